@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the batched Crafter hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run)
+
+A plain run measures the headline alone: set-up, burn-in, --warmup, the --steps timed steps, the result line.  --full
+adds everything else this file measures or checks: the sustained window, the kernel timing and roofline, the CPU
+baseline, the parity sample, the open-loop line, configs[1] / [3] / [4] and the semantic view under "extra", and for
+N > 1 the exchange alone and in blocks of 16.
+--dump-outputs DIR writes what the last timed step returned to its caller, as float32 / float64 .npy files (see
+dump_outputs): the inputs are fixed by the seeds and the action tape, so two builds can be compared output for output.
 
 One "step" = one BatchedEnv.step() over every env of every rank: Env.step (dynamics, balance, reward/done, 64x64x3
 render) with auto-reset (Env.reset worldgen) of finished envs, uniform random actions from a device-resident tape
@@ -20,10 +27,10 @@ Workload = the one BASELINE.json's metric is quoted on: 4096 envs, 64x64 world, 
 Measurement protocol (so that a short --steps window is representative): after reset() the batch runs an UNTIMED
 burn-in (--burn-in, default 400 steps: envs desynchronise, the first night and the first wave of auto-resets pass, the
 world pool is warm), then --warmup untimed steps, then EXACTLY --steps timed steps between barrier + synchronize pairs
-(max over ranks).  The dominant kernel's duration is then measured over --kernel-reps (default 300) further launches
-with HIP start / stop events attached to the kernel itself on the launch stream, whatever --steps was.
+(max over ranks).  With --full the dominant kernel's duration is then measured over --kernel-reps (default 300) further
+launches with HIP start / stop events attached to the kernel itself on the launch stream, whatever --steps was.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it has these extra objects:
   roofline     dominant kernel (crafter_step_kernel): algorithmic bytes per launch (19,742 B per env-step)
                / mean kernel duration, against the 8 TB/s HBM peak; "traffic" = PMC-counter HBM bytes per launch quoted
                from the committed profile named in "traffic_source" (not measured by this run), null if that profile
@@ -158,6 +165,25 @@ class Sampler:
             'checked': 'envs of the timed batch itself vs the CPU port (oracle, pinned against the reference): obs hash, reward, '
                        'done at every burn-in step; material map, objects, inventory, achievements, counters, chunk order, MT19937 '
                        'key + position and the frame after the last timed step'}
+
+
+DUMP_OBS_ENVS = 256   # frames written in full for this many envs (4096 whole frames as float32 would be 200 MB)
+
+
+def dump_outputs(directory, obs, reward, done, suffix=''):
+  """--dump-outputs: (obs, reward, done) of the last timed step, host copies taken before any further step, as
+  DIR/<name>.npy.  reward / done of every env; obs_sum: every env's frame summed (exact in float64); obs_sample: the
+  whole frames of DUMP_OBS_ENVS envs drawn with a fixed seed.  About 13 MB at 4096 envs."""
+  out = pathlib.Path(directory)
+  out.mkdir(parents=True, exist_ok=True)
+  arrays = {'reward': reward.astype(np.float32), 'done': done.astype(np.float32)}
+  if obs is not None:
+    n = obs.shape[0]
+    pick = np.sort(np.random.RandomState(0).choice(n, min(n, DUMP_OBS_ENVS), replace=False))
+    arrays['obs_sum'] = obs.reshape(n, -1).sum(axis=1, dtype=np.float64)
+    arrays['obs_sample'] = obs[pick].astype(np.float32)
+  for name, a in arrays.items():
+    np.save(out / f'{name}{suffix}.npy', a)
 
 
 def kernel_timing(env, tape, first, reps):
@@ -330,7 +356,12 @@ def main():
                   help='N > 1: what crosses xGMI every step (crafter_amd.dist.StepExchange modes)')
   ap.add_argument('--exchange-steps', type=int, default=1,
                   help='N > 1: steps per collective for the HEADLINE window (1 = the per-step exchange the metric names; K > 1: K records '
-                       'travel together).  The K = 16 figure is measured and reported beside it in any case (exchange_blocks_of_16)')
+                       'travel together).  With --full the K = 16 figure is measured and reported beside it (exchange_blocks_of_16)')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure and check everything beside the headline (sustained window, kernel timing / roofline, CPU '
+                       'baseline, parity, open loop, extra configs; N > 1: the exchange alone and in blocks of 16)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write (obs, reward, done) of the last timed step to DIR/*.npy (float32 / float64)')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-parity', action='store_true')
   ap.add_argument('--no-extra', action='store_true')
@@ -338,10 +369,12 @@ def main():
   ap.add_argument('--cpu-seconds', type=float, default=12.0)
   ap.add_argument('--gen-period', type=int, default=0)
   ap.add_argument('--sustained-steps', type=int, default=1000,
-                  help='a second timed window right after the --steps one (the driver times 20 steps; this is the steady state)')
+                  help='--full: a second timed window right after the --steps one (the driver times 20 steps; this is the steady state)')
   args = ap.parse_args()
   if args.exchange_steps <= 0:
     args.exchange_steps = 1
+  if not args.full:   # the headline alone: no second window, no kernel timing (the --no-* switches only matter under --full)
+    args.sustained_steps, args.kernel_reps = 0, 0
 
   import torch
   rank = int(os.environ.get('RANK', 0))
@@ -433,7 +466,7 @@ def main():
     return out
 
   exchange_main = exchange
-  want_parity = rank == 0 and not args.no_parity
+  want_parity = rank == 0 and args.full and not args.no_parity
   sampler = None
   if want_parity:
     local = sorted({0, 1, n // 2, n - 1})
@@ -490,6 +523,9 @@ def main():
   dt = dt_sync
   gpu_ms = ev0.elapsed_time(ev1)
   env.check_errors()
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, *[None if x is None else x.cpu().numpy() for x in (o if render else None, r, d)],
+                 suffix=f'_rank{rank}' if world > 1 else '')
   if sampler is not None:
     sampler.final(o)
   # sustained: the same protocol over a longer window of further steps (a 20-step window sits wherever the episode
@@ -512,7 +548,7 @@ def main():
     dt_sus = time.perf_counter() - t1
     env.check_errors()
   exchange_us = None
-  if exchange is not None:   # the exchange alone, nothing overlapping it: per-step cost if it were exposed
+  if exchange is not None and args.full:   # the exchange alone, nothing overlapping it: per-step cost if it were exposed
     torch.cuda.synchronize()
     dist.barrier()
     t2 = time.perf_counter()
@@ -526,7 +562,7 @@ def main():
   if dist is not None:
     both = torch.tensor([dt, dt_sus or 0.0, exchange_us or 0.0, host_us, dt_stream], dtype=torch.float64, device=dev)
     dist.all_reduce(both, op=dist.ReduceOp.MAX)
-    dt, dt_sus, exchange_us, host_us, dt_stream = float(both[0]), (float(both[1]) if dt_sus else None), float(both[2]), float(both[3]), float(both[4])
+    dt, dt_sus, exchange_us, host_us, dt_stream = float(both[0]), (float(both[1]) if dt_sus else None), (float(both[2]) if exchange_us is not None else None), float(both[3]), float(both[4])
     dt_sync = dt
   # N > 1: the same sustained window again with 16 steps' records per collective (what round 4 ran as its default): the
   # host then enqueues ONE collective per 16 steps.  Another workload than the metric's -- a learner sees frames up to 16
@@ -554,16 +590,8 @@ def main():
                   'note': 'the sustained protocol with 16 steps per collective: NOT the per-step exchange the metric names'}
 
   if rank == 0:
-    # dominant kernel: mean duration of crafter_step_kernel (and of the auto-reset kernel that follows it in the
-    # same call) over --kernel-reps launches, HIP events attached to the kernels on the launch stream
-    kern_us, reset_us, launches = kernel_timing(env, tape, steps_run + args.sustained_steps, args.kernel_reps)
     pool = env.pool_status()
-    kernel_name = step_kernel_name(env, render)
-    traffic, traffic_source = quoted_traffic(n, render, args.area, kernel_name)
     value = args.steps * total_envs / dt
-    per_env = (ALGO_BYTES_256 if args.area == 256 and render else ALGO_BYTES[render])
-    bytes_per_launch = per_env * n
-    achieved = bytes_per_launch / (kern_us * 1e-6) / 1e9
     workload = (f'{total_envs} envs ({n}/GPU x {world} GPU), {args.area}x{args.area} world, view 9x9, obs 64x64x3, '
                 f'random actions, auto-reset, render {"on" if render else "off"}')
     line = {
@@ -599,15 +627,24 @@ def main():
             'ms_per_step': 1000 * dt_sus / args.sustained_steps,
             'note': 'the same protocol (barrier + device synchronize on both sides) over the steps that follow the timed window'},
         'world_pool': pool,
-        'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                     'traffic': traffic, 'traffic_source': traffic_source, 'kernel': kernel_name, 'kernel_us': kern_us,
-                     'kernel_launches_timed': launches, 'reset_kernel_us': reset_us, 'algorithmic_bytes_per_launch': bytes_per_launch},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+      # dominant kernel: mean duration of crafter_step_kernel (and of the auto-reset kernel that follows it in the
+      # same call) over --kernel-reps launches, HIP events attached to the kernels on the launch stream
+      kern_us, reset_us, launches = kernel_timing(env, tape, steps_run + args.sustained_steps, args.kernel_reps)
+      kernel_name = step_kernel_name(env, render)
+      traffic, traffic_source = quoted_traffic(n, render, args.area, kernel_name)
+      per_env = (ALGO_BYTES_256 if args.area == 256 and render else ALGO_BYTES[render])
+      bytes_per_launch = per_env * n
+      achieved = bytes_per_launch / (kern_us * 1e-6) / 1e9
+      line['roofline'] = {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                          'traffic': traffic, 'traffic_source': traffic_source, 'kernel': kernel_name, 'kernel_us': kern_us,
+                          'kernel_launches_timed': launches, 'reset_kernel_us': reset_us, 'algorithmic_bytes_per_launch': bytes_per_launch}
+    if args.full and world == 1 and not args.no_cpu_baseline:
       line['cpu_baseline'] = cpu_baseline(n, args.cpu_seconds)
     if sampler is not None:
       line['parity'] = sampler.compare(tape_np, steps_run, {} if args.area == 64 else {'area': (args.area, args.area)})
-    if world == 1 and not args.no_extra and total_envs == METRIC_ENVS and args.area == 64 and render:
+    if args.full and world == 1 and not args.no_extra and total_envs == METRIC_ENVS and args.area == 64 and render:
       del env
       torch.cuda.synchronize()
       line['open_loop'] = open_loop_measurement(n, dev, 400, 64, 24, parity=not args.no_parity)

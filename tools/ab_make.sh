@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B builds of the library into gpurun_ab/<name>.so (loaded through CRAFTER_HIP_LIB; tools/ab_variants.sh alternates them on
+# A/B builds of the library into ab_builds/<name>.so (loaded through CRAFTER_HIP_LIB; tools/ab_variants.sh alternates them on
 # one GPU box).  usage: tools/ab_make.sh <name> [HEAD|tree] [-DMACRO ...]   (HEAD: the committed sources; tree: the working tree)
 set -e
 cd "$(dirname "$0")/.."
@@ -11,5 +11,5 @@ if [ "$what" = HEAD ]; then
 fi
 python -c "
 from crafter_amd import build
-print(build.build(force=True, out='gpurun_ab/$name.so', defines=($defs), root=$root))"
+print(build.build(force=True, out='ab_builds/$name.so', defines=($defs), root=$root))"
 [ -n "$tmp" ] && rm -rf "$tmp"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU box: where a balance pass spends its clocks.  Needs a PROBE BUILD (crafter_amd.build.build(out=..., defines=['CRAFTER_BALANCE_PROBE']))
 through CRAFTER_HIP_LIB: balance() accumulates shader clocks per part and leaves them in stamp slots 14, 15, 6, 12.
-usage: CRAFTER_HIP_LIB=gpurun_ab/balance_probe.so tools/gpu_balance_probe.py [envs] [--area A]"""
+usage: CRAFTER_HIP_LIB=ab_builds/balance_probe.so tools/gpu_balance_probe.py [envs] [--area A]"""
 import sys, pathlib
 import numpy as np, torch
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))

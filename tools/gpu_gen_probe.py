@@ -1,4 +1,4 @@
-"""GPU box, probe build (CRAFTER_HIP_LIB=gpurun_ab/probes.so): shader clocks per phase of the three world-generation kernels,
+"""GPU box, probe build (CRAFTER_HIP_LIB=ab_builds/probes.so): shader clocks per phase of the three world-generation kernels,
 (a) while the step loop runs beside them (the bench workload), (b) alone on the chip (the steps stopped: what a device-wide
 synchronize at the end of a timed window waits for).  usage: python tools/gpu_gen_probe.py [envs]"""
 import ctypes

@@ -15,7 +15,7 @@ if [ -n "$PMC_SQ_GROUPS" ]; then   # e.g. PMC_SQ_GROUPS="1 3 4": only these grou
 fi
 i=0
 for g in "${groups[@]}"; do
-  rocprofv3 --pmc $g --output-format csv -d $out/g$i -- python $root/bench.py --steps 200 --warmup 50 --burn-in 200 --kernel-reps 10 --no-cpu-baseline --no-parity --no-extra --sustained-steps 0 "$@" > $out/g$i.log 2>&1
+  rocprofv3 --pmc $g --output-format csv -d $out/g$i -- python $root/bench.py --full --steps 200 --warmup 50 --burn-in 200 --kernel-reps 10 --no-cpu-baseline --no-parity --no-extra --sustained-steps 0 "$@" > $out/g$i.log 2>&1
   i=$((i+1))
 done
 python - $out <<'PY' | tee $root/gpurun_out/pmc_sq.txt

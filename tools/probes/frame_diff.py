@@ -1,9 +1,9 @@
-"""GPU box debugging aid: which pixels of which envs differ from oracle frames saved beforehand (gpurun_ab/oracle37.npz)."""
+"""GPU box debugging aid: which pixels of which envs differ from oracle frames saved beforehand (ab_builds/oracle37.npz)."""
 import sys, os
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from crafter_amd import BatchedEnv
-ref = np.load('gpurun_ab/oracle37.npz')
+ref = np.load('ab_builds/oracle37.npz')
 n = 4096
 tapes = np.random.RandomState(1234).randint(0, 17, size=(300, n)).astype(np.int32)
 env = BatchedEnv(n, seed=1000, auto_reset=True)

@@ -14,9 +14,9 @@ P="--no-cpu-baseline --no-parity --no-extra --sustained-steps 0"
 prof() {   # name, envs, area, render, bench args
   name=$1; envs=$2; area=$3; render=$4; shift 4
   rm -rf $out/${name}_stats $out/${name}_fetch $out/${name}_write
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${name}_stats -- python $root/bench.py $P "$@" --steps 600 --warmup 100 --burn-in 300 --kernel-reps 50 > $out/${name}_stats.log 2>&1
-  timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/${name}_fetch -- python $root/bench.py $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_fetch.log 2>&1
-  timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/${name}_write -- python $root/bench.py $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_write.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${name}_stats -- python $root/bench.py --full $P "$@" --steps 600 --warmup 100 --burn-in 300 --kernel-reps 50 > $out/${name}_stats.log 2>&1
+  timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/${name}_fetch -- python $root/bench.py --full $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_fetch.log 2>&1
+  timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/${name}_write -- python $root/bench.py --full $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_write.log 2>&1
   (cd $root && python tools/summarize_profile.py $name $out/${name}_stats $out/${name}_fetch $out/${name}_write $envs $area $render > $out/${name}_summary.log 2>&1)
   cp $root/profiles/${name}_kernel_stats.csv $root/profiles/${name}_hbm_traffic.json $out/${tag}_profiles/ 2> /dev/null
   rm -rf $out/${name}_stats $out/${name}_fetch $out/${name}_write
@@ -69,8 +69,8 @@ timeout 200 python tools/host_overhead_dist.py 512 2>&1 | grep "envs,\|scatter" 
 timeout 200 python tools/gpu_phase_means.py 4096 > $out/${tag}_profiles/${tag}_phases_4096.txt 2>&1
 timeout 200 python tools/gpu_rollout_phases.py 4096 > $out/${tag}_profiles/${tag}_rollout_phases_4096.txt 2>&1
 timeout 300 python tools/gpu_rollout_ab.py 1536,3072,4096,4608,6144,8192 default > $out/${tag}_profiles/${tag}_rollout_batch_sweep.txt 2>&1
-timeout 900 python bench.py > $out/${tag}_profiles/${tag}_bench.json 2> $out/${tag}_bench.err
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/${tag}_profiles/${tag}_bench_driver.json 2> $out/${tag}_bench_driver.err
+timeout 900 python bench.py --full > $out/${tag}_profiles/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/${tag}_profiles/${tag}_bench_driver.json 2> $out/${tag}_bench_driver.err
 cp $out/${tag}_pytest_gpu.txt $out/${tag}_profiles/
 python - <<PY
 import json

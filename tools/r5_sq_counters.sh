@@ -13,7 +13,7 @@ groups=("SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY"
         "SQC_DCACHE_REQ SQC_DCACHE_MISSES SQC_DCACHE_HITS SQ_INST_LEVEL_LDS")
 i=0
 for g in "${groups[@]}"; do
-  timeout 200 rocprofv3 --pmc $g --output-format csv -d $out/g$i -- python $root/bench.py --steps 200 --warmup 50 --burn-in 200 --kernel-reps 10 --no-cpu-baseline --no-parity --no-extra --sustained-steps 0 > $out/g$i.log 2>&1
+  timeout 200 rocprofv3 --pmc $g --output-format csv -d $out/g$i -- python $root/bench.py --full --steps 200 --warmup 50 --burn-in 200 --kernel-reps 10 --no-cpu-baseline --no-parity --no-extra --sustained-steps 0 > $out/g$i.log 2>&1
   i=$((i+1))
 done
 python - $out <<'PY' | tee $root/gpurun_out/r5_sq_counters.txt

@@ -1,9 +1,9 @@
 #!/bin/bash
-# GPU box: same-box A/B of library builds gpurun_ab/<name>.so at several batch sizes (closed loop, 1500 steps + 1000 sustained)
+# GPU box: same-box A/B of library builds ab_builds/<name>.so at several batch sizes (closed loop, 1500 steps + 1000 sustained)
 # usage: tools/r6_ab.sh "4096 1024" name1 name2 ...
 sizes=$1; shift
 for n in $sizes; do for i in 1 2; do for v in "$@"; do
-  CRAFTER_HIP_LIB=gpurun_ab/$v.so timeout 200 python bench.py --envs $n --steps 1500 --warmup 100 --no-cpu-baseline --no-parity --no-extra 2> /tmp/ab_err.txt | python -c "
+  CRAFTER_HIP_LIB=ab_builds/$v.so timeout 200 python bench.py --full --envs $n --steps 1500 --warmup 100 --no-cpu-baseline --no-parity --no-extra 2> /tmp/ab_err.txt | python -c "
 import sys, json
 try:
   d = json.loads(sys.stdin.read().strip().splitlines()[-1])

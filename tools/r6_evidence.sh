@@ -5,7 +5,7 @@
 # kernels (VERDICT r5 #1b), phase stamps of the step kernels and of the three generation kernels (probe build), the host's share
 # of the N > 1 loop body, the bench lines.  Profiles are summarised ON the box (-> gpurun_out/<tag>_profiles/) so that the bench
 # lines that follow quote the traffic measured on these very sources.
-# usage: tools/r6_evidence.sh <tag>     (needs gpurun_ab/probes.so: tools/ab_make.sh probes tree -DCRAFTER_PROBES)
+# usage: tools/r6_evidence.sh <tag>     (needs ab_builds/probes.so: tools/ab_make.sh probes tree -DCRAFTER_PROBES)
 tag=${1:-r6}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out
@@ -17,9 +17,9 @@ P="--no-cpu-baseline --no-parity --no-extra --sustained-steps 0"
 prof() {   # name, envs, area, render, bench args
   name=$1; envs=$2; area=$3; render=$4; shift 4
   rm -rf ${out:?}/${name}_stats $out/${name}_fetch $out/${name}_write
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${name}_stats -- python $root/bench.py $P "$@" --steps 600 --warmup 100 --burn-in 300 --kernel-reps 50 > $out/${name}_stats.log 2>&1
-  timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/${name}_fetch -- python $root/bench.py $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_fetch.log 2>&1
-  timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/${name}_write -- python $root/bench.py $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_write.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${name}_stats -- python $root/bench.py --full $P "$@" --steps 600 --warmup 100 --burn-in 300 --kernel-reps 50 > $out/${name}_stats.log 2>&1
+  timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/${name}_fetch -- python $root/bench.py --full $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_fetch.log 2>&1
+  timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/${name}_write -- python $root/bench.py --full $P "$@" --steps 200 --warmup 50 --burn-in 200 --kernel-reps 20 > $out/${name}_write.log 2>&1
   (cd $root && python tools/summarize_profile.py $name $out/${name}_stats $out/${name}_fetch $out/${name}_write $envs $area $render > $out/${name}_summary.log 2>&1)
   cp $root/profiles/${name}_kernel_stats.csv $root/profiles/${name}_hbm_traffic.json $out/${tag}_profiles/ 2> /dev/null
   if [ "$name" = "$tag" ]; then python $root/tools/trace_gaps.py $out/${name}_stats > $out/${tag}_profiles/${tag}_launch_gaps.txt 2>&1; fi
@@ -73,21 +73,21 @@ cd $root
 sq=$out/${tag}_sq; rm -rf ${sq:?}; mkdir -p $sq
 i=0
 for g in "SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU"; do
-  (cd /tmp && timeout 200 rocprofv3 --pmc $g --output-format csv -d $sq/g$i -- python $root/bench.py --steps 200 --warmup 50 --burn-in 200 --kernel-reps 10 $P > $sq/g$i.log 2>&1)
+  (cd /tmp && timeout 200 rocprofv3 --pmc $g --output-format csv -d $sq/g$i -- python $root/bench.py --full --steps 200 --warmup 50 --burn-in 200 --kernel-reps 10 $P > $sq/g$i.log 2>&1)
   i=$((i+1))
 done
 python tools/sq_summary.py $sq > $out/${tag}_profiles/${tag}_sq_counters.txt
 rm -rf ${sq:?}
-CRAFTER_HIP_LIB=gpurun_ab/probes.so timeout 200 python tools/gpu_gen_probe.py 2>&1 | grep -v amdgpu > $out/${tag}_profiles/${tag}_gen_phases.txt
+CRAFTER_HIP_LIB=ab_builds/probes.so timeout 200 python tools/gpu_gen_probe.py 2>&1 | grep -v amdgpu > $out/${tag}_profiles/${tag}_gen_phases.txt
 timeout 200 python tools/host_overhead_dist.py 512 2>&1 | grep "envs,\|scatter\|native\|from C" > $out/${tag}_profiles/${tag}_host_overhead_dist.txt
 timeout 200 python tools/gpu_phase_means.py 1024 > $out/${tag}_profiles/${tag}_phases_1024.txt 2>&1
-CRAFTER_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --envs 512 --steps 600 --warmup 50 --no-extra --no-cpu-baseline > $out/${tag}_profiles/${tag}_bench_exchange_1rank.json 2> $out/${tag}_bench_exchange.err
+CRAFTER_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --full --envs 512 --steps 600 --warmup 50 --no-extra --no-cpu-baseline > $out/${tag}_profiles/${tag}_bench_exchange_1rank.json 2> $out/${tag}_bench_exchange.err
 timeout 200 python tools/gpu_phase_means.py 4096 > $out/${tag}_profiles/${tag}_phases_4096.txt 2>&1
 timeout 200 python tools/gpu_rollout_phases.py 4096 > $out/${tag}_profiles/${tag}_rollout_phases_4096.txt 2>&1
 timeout 300 python tools/gpu_rollout_ab.py 1536,3072,4096,4608,6144,8192 default > $out/${tag}_profiles/${tag}_rollout_batch_sweep.txt 2>&1
-timeout 900 python bench.py > $out/${tag}_profiles/${tag}_bench.json 2> $out/${tag}_bench.err
-for i in 1 2 3; do timeout 900 python bench.py --steps 20 --warmup 5 --no-extra > $out/${tag}_profiles/${tag}_bench_driver_$i.json 2> $out/${tag}_bench_driver.err; done
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/${tag}_profiles/${tag}_bench_driver.json 2>> $out/${tag}_bench_driver.err
+timeout 900 python bench.py --full > $out/${tag}_profiles/${tag}_bench.json 2> $out/${tag}_bench.err
+for i in 1 2 3; do timeout 900 python bench.py --full --steps 20 --warmup 5 --no-extra > $out/${tag}_profiles/${tag}_bench_driver_$i.json 2> $out/${tag}_bench_driver.err; done
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/${tag}_profiles/${tag}_bench_driver.json 2>> $out/${tag}_bench_driver.err
 cp $out/${tag}_pytest_gpu.txt $out/${tag}_profiles/
 python - <<PY
 import json

@@ -2,11 +2,11 @@
 # GPU box (round 6): which resource of a resident generation workgroup displaces step workgroups -- LDS or registers?
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $root
-export CRAFTER_HIP_LIB=gpurun_ab/probes.so
+export CRAFTER_HIP_LIB=ab_builds/probes.so
 line() {
   label=$1; shift
   for i in 1 2; do
-    env "$@" timeout 300 python bench.py --steps 1000 --warmup 100 --no-cpu-baseline --no-parity --no-extra --kernel-reps 100 --sustained-steps 0 2> /tmp/err.txt | python -c "
+    env "$@" timeout 300 python bench.py --full --steps 1000 --warmup 100 --no-cpu-baseline --no-parity --no-extra --kernel-reps 100 --sustained-steps 0 2> /tmp/err.txt | python -c "
 import sys, json
 try:
   d = json.loads(sys.stdin.read().strip().splitlines()[-1])
