@@ -7,6 +7,7 @@ class only allocates them, uploads the host-evaluated tables and enqueues kernel
 torch stream.  There is no CPU implementation behind it.
 """
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -14,11 +15,44 @@ import torch
 
 from . import abi, lib as _libmod, state, tables
 
-_TORCH_DTYPE = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint32: torch.int32, np.int32: torch.int32}
+_TORCH_DTYPE = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint32: torch.int32, np.int32: torch.int32, np.float32: torch.float32}
 
 
 class CrafterDeviceError(RuntimeError):
   pass
+
+
+class EnvStore:
+  """Copies of env rows taken by BatchedEnv.save_state: each env's state (no world-pool buffers, no queues) and its last obs /
+  reward / done, in device tensors (or host tensors after .cpu(), e.g. for pickling), with the geometry they were taken with.
+  BatchedEnv.load_state writes them into rows of any batch of the same geometry."""
+
+  def __init__(self, tensors, geometry, idx):
+    self.tensors = tensors
+    self.geometry = dict(geometry)
+    self.idx = idx   # the rows the store was taken from (load_state's default destination)
+
+  def __len__(self):
+    return int(self.tensors['rec'].shape[0])
+
+  @property
+  def device(self):
+    return self.tensors['rec'].device
+
+  @property
+  def max_objects(self):
+    return int(self.tensors['objs'].shape[1])
+
+  def to(self, device):
+    return EnvStore({k: v.to(device) for k, v in self.tensors.items()}, self.geometry, self.idx)
+
+  def cpu(self):
+    return self.to('cpu')
+
+  def _ptrs(self):
+    ptrs = {name: None for name, _ in abi.StatePtrs._fields_}
+    ptrs.update({k: v.data_ptr() for k, v in self.tensors.items() if k in ptrs})
+    return abi.StatePtrs(**ptrs)
 
 
 class _Handle:
@@ -377,6 +411,100 @@ class BatchedEnv:
     if self.cfg.want_semantic:
       out['semantic'] = self.state['semantic'].view(self.num_envs, self.cfg.W, self.cfg.H)
     return out
+
+  # ------------------------------------------------------------------ copies of envs
+  def _index(self, idx, rows, what):
+    """-> (contiguous device int32 tensor, host-checked).  Host indices (lists, numpy, CPU tensors) are range-checked here and
+    raise ValueError before anything is enqueued; device tensors are checked by the library on the device (ST_BAD_COPY)."""
+    if torch.is_tensor(idx) and idx.is_cuda:
+      if idx.device != self.device:
+        raise ValueError(f'{what}: index tensor on {idx.device}, batch on {self.device}')
+      return idx.reshape(-1).to(torch.int32).contiguous(), None
+    a = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx).reshape(-1)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+      raise ValueError(f'{what}: indices must be integers')
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= rows):
+      raise ValueError(f'{what}: index out of range 0 .. {rows - 1}')
+    return torch.from_numpy(a.astype(np.int32)).to(self.device), a
+
+  def _geometry(self):
+    return dict(area=(int(self.cfg.W), int(self.cfg.H)), view=tuple(int(v) for v in self._ctor['view']),
+                size=(int(self.cfg.size_w), int(self.cfg.size_h)), length=int(self.cfg.length),
+                rules=hashlib.sha256(self.tables.rules_bytes().tobytes()).hexdigest()[:16], semantic=bool(self.cfg.want_semantic),
+                slot_map_derived=self.slot_map_derived)
+
+  def copy_envs(self, src, dst):
+    """Env dst[i] becomes an exact copy of env src[i] (what copy.deepcopy of the reference's crafter.Env carries, and the obs /
+    reward / done rows), as it stands after every call enqueued so far; stepped on, it lives the future the source would have,
+    later episodes included.  Enqueued on the current stream.  A destination named twice or also named as a source is refused:
+    host indices raise ValueError, device indices refuse the whole call on the device (check_errors: ST_BAD_COPY)."""
+    s, hs = self._index(src, self.num_envs, 'src')
+    d, hd = self._index(dst, self.num_envs, 'dst')
+    if s.numel() != d.numel():
+      raise ValueError('src and dst must have the same length')
+    if hd is not None and len(np.unique(hd)) != len(hd):
+      raise ValueError('dst names an env twice')
+    if hs is not None and hd is not None and np.intersect1d(hs, hd).size:
+      raise ValueError('an env is both a source and a destination')
+    with torch.cuda.device(self.device):
+      self._check(self._lib.crafter_copy_envs(
+          self._handle, C.c_void_p(s.data_ptr()), C.c_void_p(d.data_ptr()), int(s.numel()), C.c_void_p(self.obs.data_ptr()),
+          C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.done.data_ptr()), self._stream()))
+    self._keep = (s, d)
+
+  def save_state(self, idx=None):
+    """-> EnvStore holding copies of envs idx (all by default) as they stand after every call enqueued so far."""
+    i, _ = self._index(np.arange(self.num_envs) if idx is None else idx, self.num_envs, 'idx')
+    rows = int(i.numel())
+    spec = state.store_spec(self.cfg, rows, self.slot_map_derived)
+    store = EnvStore({k: torch.zeros(shape, dtype=_TORCH_DTYPE[dt], device=self.device) for k, (shape, dt) in spec.items()},
+                     self._geometry(), i)
+    t = store.tensors
+    ptrs = store._ptrs()
+    with torch.cuda.device(self.device):
+      self._check(self._lib.crafter_save_envs(
+          self._handle, C.c_void_p(i.data_ptr()), rows, C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()),
+          C.c_void_p(self.done.data_ptr()), C.byref(ptrs), rows, store.max_objects, C.c_void_p(t['obs'].data_ptr()),
+          C.c_void_p(t['reward'].data_ptr()), C.c_void_p(t['done'].data_ptr()), self._stream()))
+    self._keep = i
+    return store
+
+  def load_state(self, store, idx=None, rows=None):
+    """Writes store rows `rows` (all by default) into envs idx (by default the envs the store was taken from), which then go on
+    exactly as the saved envs would have.  The store must come from a batch of the same area, view, size, rules and length on
+    this device; a store with a wider slot table grows this batch first (_grow_objects)."""
+    mine, theirs = self._geometry(), store.geometry
+    for key in ('area', 'view', 'size', 'length', 'rules', 'slot_map_derived'):
+      if mine[key] != theirs[key]:
+        raise ValueError(f'load_state: the store was taken with another {key} than this batch has')
+    if mine['semantic'] and not theirs['semantic']:
+      raise ValueError('load_state: this batch keeps info["semantic"], the store was taken without it')
+    if store.device != self.device:
+      raise ValueError(f'load_state: the store is on {store.device}, the batch on {self.device} (EnvStore.to)')
+    if store.max_objects > self.cfg.max_objects:
+      self._grow_objects(store.max_objects)
+    d, hd = self._index(store.idx if idx is None else idx, self.num_envs, 'idx')
+    if hd is not None and len(np.unique(hd)) != len(hd):
+      raise ValueError('idx names an env twice')
+    r = None
+    if rows is not None:
+      r, _ = self._index(rows, len(store), 'rows')
+      if r.numel() != d.numel():
+        raise ValueError('rows and idx must have the same length')
+    elif d.numel() > len(store):
+      raise ValueError('idx is longer than the store')
+    t = store.tensors
+    ptrs = store._ptrs()
+    with torch.cuda.device(self.device):
+      self._check(self._lib.crafter_load_envs(
+          self._handle, C.byref(ptrs), len(store), store.max_objects, C.c_void_p(t['obs'].data_ptr()),
+          C.c_void_p(t['reward'].data_ptr()), C.c_void_p(t['done'].data_ptr()), None if r is None else C.c_void_p(r.data_ptr()),
+          C.c_void_p(d.data_ptr()), int(d.numel()), C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()),
+          C.c_void_p(self.done.data_ptr()), self._stream()))
+    self._keep = (store, r, d)
+    if self._unbounded:   # a loaded episode may be longer than any this batch ran: the next _grow_daylight reads the counters
+      self._step_bound = self.cfg.n_daylight
 
   # ------------------------------------------------------------------ measurement
   def enable_phase_stamps(self, enable=True):

@@ -19,6 +19,7 @@
 #include "../../include/crafter_hip.h"
 #include "crafter_rollout.hpp"
 #include "dispatch_order.hpp"
+#include "env_copy.hpp"
 #include "env_kernels.hpp"
 #include "wave_gfx950.hpp"
 
@@ -93,6 +94,7 @@ static_assert(cabi::CRAFTER_TEX_COUNT == TEX_COUNT && cabi::CRAFTER_TEX_PLANT_RI
                   CRAFTER_MAX_ACTIONS == MAX_ACTIONS && CRAFTER_MAX_PLACE == MAX_PLACE && CRAFTER_MAX_MAKE == MAX_MAKE &&
                   CRAFTER_MAX_USES == MAX_USES && CRAFTER_CHUNK == CHUNK,
               "constants of crafter_hip_types.h");
+static_assert(cabi::CRAFTER_ST_BAD_COPY == ST_BAD_COPY && cabi::CRAFTER_ST_POOL_MISMATCH == ST_POOL_MISMATCH, "status bits of crafter_hip_types.h");
 
 namespace {
 
@@ -573,6 +575,10 @@ struct crafter_handle {
   int gen_parity = 0;          // segment collecting requests now
   int steps_since_gen = 0;
   int gen_period = 8;
+  // crafter_copy_envs / _save_envs / _load_envs: the index check's per-row marks ([N], stamped with copy_stamp) and verdict
+  int32_t* copy_mark = nullptr;
+  int32_t* copy_verdict = nullptr;
+  int32_t copy_stamp = 0;
   // optional per-kernel timing (HIP events on the launch stream)
   bool timing = false;
   std::vector<hipEvent_t> events;   // triples: before step, between, after reset
@@ -1087,6 +1093,101 @@ int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* st
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_reset launch", e);
   return 0;
+}
+
+// Copies of envs read and write rows of the world pool (crafter_copy_envs: the source's two entries go along; crafter_load_envs:
+// the destination's entries are emptied).  Before that every pool row must be at rest, exactly as before crafter_reset: the
+// segment collecting requests now is launched as a batch (no request stays queued with PoolHdr.pending set, which would block
+// its entry for later requests), the launch stream is ordered behind every launched batch (hipStreamWaitEvent: the host does
+// not block) and all of them are trusted.  Batches launched afterwards wait for the copy (ev_main, pool_schedule).
+static void pool_quiesce(crafter_handle* h, hipStream_t stream) {
+  if (!h->pool || h->pool_failed) return;
+  pool_schedule(h, stream, h->gen_period);
+  for (uint32_t s = h->safe_seq + 1; s <= h->batches && !h->pool_failed; s++) {
+    hipError_t ew = hipStreamWaitEvent(stream, h->ev_gen[s % kGenRing], 0);
+    if (ew != hipSuccess) pool_fail(h, "hipStreamWaitEvent(copy)", ew);
+  }
+  if (!h->pool_failed) h->safe_seq = h->batches;
+}
+
+// The index check, then the copy (env_copy.hpp).  pool_rows: the pool is at rest and both sides are the bound state.
+static int launch_copy(crafter_handle* h, const char* who, int mode, const CopySide& a, const CopySide& b, const int32_t* sidx,
+                       const int32_t* didx, int n, hipStream_t stream, bool pool_rows) {
+  CopyPlan plan;
+  if (!make_copy_plan(plan, h->cfg, a, b, mode, !lds_layout(h->cfg).maps_in_lds, (size_t)h->cfg.size_w * h->cfg.size_h * 3, pool_rows))
+    return fail(h, std::string(who) + ": too many buffers for one copy plan");
+  if (!h->copy_mark) {
+    hipError_t ea = hipMalloc((void**)&h->copy_mark, ((size_t)h->cfg.num_envs + 1) * sizeof(int32_t));
+    if (ea != hipSuccess) return hip_fail(h, who, ea);
+    h->owned.push_back(h->copy_mark);
+    h->copy_verdict = h->copy_mark + h->cfg.num_envs;
+    h->copy_stamp = 0;
+  }
+  if (h->copy_stamp <= 0 || h->copy_stamp == 0x7fffffff) {   // first call, or the stamps wrapped: start the marks afresh
+    hipError_t em = hipMemsetAsync(h->copy_mark, 0, (size_t)h->cfg.num_envs * sizeof(int32_t), stream);
+    if (em != hipSuccess) return hip_fail(h, who, em);
+    h->copy_stamp = 0;
+  }
+  const int32_t stamp = ++h->copy_stamp;
+  hipLaunchKernelGGL(crafter_copy_check_kernel, dim3(1), dim3(kCheckThreads), 0, stream, sidx, didx, n, a.rows, b.rows, mode, stamp,
+                     h->copy_mark, h->copy_verdict, (EnvRec*)h->st.rec, h->cfg.num_envs);
+  hipLaunchKernelGGL(crafter_copy_envs_kernel, dim3((unsigned)((long long)n * plan.parts)), dim3(kCopyThreads), 0, stream, plan, sidx,
+                     didx, n, (const int32_t*)h->copy_verdict);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, who, e);
+  return 0;
+}
+
+static int check_store(crafter_handle* h, const char* who, const crafter_state_ptrs* store, int32_t rows, int32_t max_objects) {
+  if (!store || rows < 0 || max_objects < 1) return fail(h, std::string(who) + ": bad store");
+  const StatePtrs& s = *store;
+  if (!s.mat || !s.objs || !s.mt || !s.rec || !s.chunk_order || !s.chunk_seen || !s.census)
+    return fail(h, std::string(who) + ": null store buffer");
+  if (!lds_layout(h->cfg).maps_in_lds && !s.objmap) return fail(h, std::string(who) + ": this world keeps its slot map in HBM: the store needs objmap");
+  if (s.pool_mat || s.pool_hdr || s.gen_q || s.gen_latest) return fail(h, std::string(who) + ": a store holds no pool buffers or queues");
+  return 0;
+}
+
+int crafter_copy_envs(crafter_handle* h, const int32_t* src, const int32_t* dst, int32_t n, uint8_t* obs, float* reward, uint8_t* done,
+                      void* stream) {
+  if (ready(h, "crafter_copy_envs")) return 1;
+  if (n < 0 || (n > 0 && (!src || !dst))) return fail(h, "crafter_copy_envs: bad index arrays");
+  if (n == 0) return 0;
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  pool_quiesce(h, (hipStream_t)stream);
+  const int N = h->cfg.num_envs;
+  CopySide side{&h->st, N, h->cfg.max_objects, obs, reward, done};
+  return launch_copy(h, "crafter_copy_envs", COPY_WITHIN, side, side, src, dst, n, (hipStream_t)stream, h->pool && !h->pool_failed);
+}
+
+int crafter_save_envs(crafter_handle* h, const int32_t* idx, int32_t n, const uint8_t* obs, const float* reward, const uint8_t* done,
+                      const crafter_state_ptrs* store, int32_t store_rows, int32_t store_max_objects, uint8_t* store_obs,
+                      float* store_reward, uint8_t* store_done, void* stream) {
+  if (ready(h, "crafter_save_envs")) return 1;
+  if (check_store(h, "crafter_save_envs", store, store_rows, store_max_objects)) return 1;
+  if (n < 0 || n > store_rows) return fail(h, "crafter_save_envs: n outside 0 .. store_rows");
+  if (store_max_objects < h->cfg.max_objects) return fail(h, "crafter_save_envs: the store's slot table is narrower than the batch's");
+  if (n == 0) return 0;
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;   // (reads live rows only: the pool's side streams never write them)
+  CopySide a{&h->st, h->cfg.num_envs, h->cfg.max_objects, obs, reward, done};
+  CopySide b{store, store_rows, store_max_objects, store_obs, store_reward, store_done};
+  return launch_copy(h, "crafter_save_envs", COPY_SAVE, a, b, idx, nullptr, n, (hipStream_t)stream, false);
+}
+
+int crafter_load_envs(crafter_handle* h, const crafter_state_ptrs* store, int32_t store_rows, int32_t store_max_objects,
+                      const uint8_t* store_obs, const float* store_reward, const uint8_t* store_done, const int32_t* rows,
+                      const int32_t* idx, int32_t n, uint8_t* obs, float* reward, uint8_t* done, void* stream) {
+  if (ready(h, "crafter_load_envs")) return 1;
+  if (check_store(h, "crafter_load_envs", store, store_rows, store_max_objects)) return 1;
+  if (n < 0 || (n > 0 && !idx)) return fail(h, "crafter_load_envs: bad index arrays");
+  if (store_max_objects > h->cfg.max_objects) return fail(h, "crafter_load_envs: the store's slot table is wider than the batch's (grow the batch first)");
+  if (h->cfg.want_semantic && !store->semantic) return fail(h, "crafter_load_envs: the batch keeps info['semantic'], the store does not");
+  if (n == 0) return 0;
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  pool_quiesce(h, (hipStream_t)stream);
+  CopySide a{store, store_rows, store_max_objects, store_obs, store_reward, store_done};
+  CopySide b{&h->st, h->cfg.num_envs, h->cfg.max_objects, obs, reward, done};
+  return launch_copy(h, "crafter_load_envs", COPY_LOAD, a, b, rows, idx, n, (hipStream_t)stream, false);
 }
 
 // A launch with start / stop events attached (timing mode: hipExtLaunchKernelGGL) or a plain one -- the plain launch is

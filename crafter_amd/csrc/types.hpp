@@ -34,6 +34,8 @@ enum : uint32_t {
   ST_POOL_MISMATCH = 16u,  // a pooled world trusted by the scheduler did not hold the episode it was adopted for
   ST_PIPE_STALL = 32u,     // a bounded in-kernel wait ran out (no kernel of this build waits inside a launch: reserved; the
                            //   pipelined step kernel that set it was removed in round 5)
+  ST_BAD_COPY = 64u,       // crafter_copy_envs / _save_envs / _load_envs refused its indices (out of range, a destination named
+                           //   twice, or one that is also a source): nothing was copied
 };
 
 // One world object = one 16-byte record (one dwordx4 / ds_read_b128).

@@ -88,6 +88,7 @@ class Env(BaseClass):
     self._length = length
     self._seed = seed
     self._episode = 0
+    self._rules = rules
     self._batch = batched.BatchedEnv(
         1, area, tuple(int(v) for v in view), tuple(int(s) for s in size), reward, length, seeds=[seed],
         device=device, auto_reset=False, semantic=True, render=True, rules=rules)
@@ -96,6 +97,33 @@ class Env(BaseClass):
     self._step = None
     self.reward_range = None
     self.metadata = None
+
+  # copy.deepcopy / pickle (the reference's Env is a plain Python object: both carry the whole world, the RNG, _seed and
+  # _episode).  The copy is a new Env -- its own native handle -- whose device row is loaded from the original's.
+  def _ctor_args(self):
+    return dict(area=self._area, view=tuple(int(v) for v in self._view), size=tuple(int(v) for v in self._size), reward=self._reward,
+                length=self._length, seed=self._seed, rules=self._rules)
+
+  def _restore(self, host, store, device):
+    Env.__init__(self, device=device, **host['ctor'])
+    self._episode, self._step = host['episode'], host['step']
+    self._player = _PlayerView(self) if host['player'] else None
+    self._batch.load_state(store.to(self._batch.device), [0], [0])
+
+  def _host_fields(self):
+    return {'ctor': self._ctor_args(), 'episode': self._episode, 'step': self._step, 'player': self._player is not None}
+
+  def __deepcopy__(self, memo):
+    new = Env.__new__(Env)
+    memo[id(self)] = new
+    new._restore(self._host_fields(), self._batch.save_state([0]), self._batch.device)
+    return new
+
+  def __getstate__(self):
+    return {'host': self._host_fields(), 'store': self._batch.save_state([0]).cpu()}
+
+  def __setstate__(self, state):
+    self._restore(state['host'], state['store'], 'cuda')
 
   @property
   def observation_space(self):

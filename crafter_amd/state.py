@@ -38,6 +38,26 @@ def state_spec(cfg):
   }
 
 
+# What a copy of an env carries: its state rows, without the world pool's buffers or the request queues.
+STORE_BUFFERS = ('mat', 'objmap', 'objs', 'mt', 'rec', 'chunk_order', 'chunk_seen', 'census', 'terminal', 'semantic')
+
+
+def store_spec(cfg, rows, slot_map_derived=True):
+  """name -> (shape, numpy dtype) of the buffers an EnvStore of `rows` envs holds: the state rows (objmap only where the
+  cell -> slot map is state, i.e. not slot_map_derived; semantic only with want_semantic) and the last obs / reward / done."""
+  spec = state_spec(cfg)
+  out = {}
+  for name in STORE_BUFFERS:
+    if (name == 'objmap' and slot_map_derived) or (name == 'semantic' and not cfg.want_semantic):
+      continue
+    shape, dt = spec[name]
+    out[name] = ((rows,) + tuple(shape[1:]), dt)
+  out['obs'] = ((rows, cfg.size_h, cfg.size_w, 3), np.uint8)
+  out['reward'] = ((rows,), np.float32)
+  out['done'] = ((rows,), np.uint8)
+  return out
+
+
 POOL_BUFFERS = ('pool_mat', 'pool_objs', 'pool_mt', 'pool_hdr', 'pool_chunk_order', 'gen_q', 'gen_latest', 'pool_stats', 'pool_perm', 'pool_census')
 
 

@@ -63,7 +63,8 @@ typedef struct crafter_host_tables {
 /* sizeof(Obj, EnvRec, Rules, Config, StatePtrs, TablePtrs) as compiled, for binding self-checks. */
 void crafter_struct_sizes(int32_t out[6]);
 
-/* ABI revision of this header. */
+/* ABI revision of this header.  Revision 7 includes the additive entry points crafter_copy_envs, crafter_save_envs and
+ * crafter_load_envs (and the status bit CRAFTER_ST_BAD_COPY): a binding looks them up by name. */
 int32_t crafter_abi_version(void);
 
 /* Replaces Env.__init__ (env.py:27-56) for a batch of cfg->num_envs environments. */
@@ -122,6 +123,35 @@ int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* st
  * info[...] of the reference is read from the bound state buffers (EnvRec.inv/ach/..., semantic). */
 int crafter_step(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
                  void* stream);
+/* Copies of whole environments (the reference's copy.deepcopy / pickle of a crafter.Env carries everything below).  An env
+ * row is: mat, objs (the whole slot table), mt, rec (step / episode counters, seed lane, sticky status...), chunk_order,
+ * chunk_seen, census, terminal, semantic (if kept), objmap (only where crafter_slot_map_derived() == 0) and the row of the
+ * caller's obs / reward / done buffers (NULL: not copied).  DESIGN.md 3 lists what is state, derived and scratch.
+ * Indices are device int32 arrays.  They are checked on the device before anything is copied: an index out of range, a
+ * destination named twice, or (crafter_copy_envs) a destination that is also a source refuses the WHOLE call -- no row
+ * changes -- and sets CRAFTER_ST_BAD_COPY in the status of the bound-state rows it names (row 0 if none exists).
+ *
+ * crafter_copy_envs: row dst[i] of the bound state becomes an exact copy of row src[i], i < n, as it stands after every call
+ *   enqueued before.  With the world pool running the source's two pooled worlds go along, so that the copy's later episodes
+ *   come from the pool too.  Before the copy the pool is brought to rest: the requests collected so far are launched as a batch
+ *   and the stream waits (on the device) for every batch launched; the cost is measured in DESIGN.md 9.
+ * A store: a crafter_state_ptrs with the pool and queue pointers NULL (objmap only where the map is state, semantic only if
+ *   kept), `store_rows` rows and a slot table of `store_max_objects` entries, plus obs / reward / done rows of the batch's
+ *   layout.  Geometry, view, size, rules and length are those of the handle; the caller keeps them equal.
+ * crafter_save_envs: store row i <- bound row idx[i], i < n <= store_rows; store_max_objects >= the handle's.  Reads live rows
+ *   only: no wait for the pool.
+ * crafter_load_envs: bound row idx[i] <- store row rows[i] (rows NULL: i); store_max_objects <= the handle's (a narrower
+ *   table is zero-padded).  The destination's pool entries are emptied: it regenerates its next world inline once (same
+ *   generator, same (seed, episode): unobservable) and the pool takes over again.  Brings the pool to rest first, as above. */
+int crafter_copy_envs(crafter_handle* h, const int32_t* src, const int32_t* dst, int32_t n, uint8_t* obs, float* reward, uint8_t* done,
+                      void* stream);
+int crafter_save_envs(crafter_handle* h, const int32_t* idx, int32_t n, const uint8_t* obs, const float* reward, const uint8_t* done,
+                      const crafter_state_ptrs* store, int32_t store_rows, int32_t store_max_objects, uint8_t* store_obs,
+                      float* store_reward, uint8_t* store_done, void* stream);
+int crafter_load_envs(crafter_handle* h, const crafter_state_ptrs* store, int32_t store_rows, int32_t store_max_objects,
+                      const uint8_t* store_obs, const float* store_reward, const uint8_t* store_done, const int32_t* rows,
+                      const int32_t* idx, int32_t n, uint8_t* obs, float* reward, uint8_t* done, void* stream);
+
 /* Streams: a handle's calls are ordered by the stream they are issued on.  Changing the stream between two calls
  * (crafter_reset on one, crafter_step on another) is allowed: the library makes the new stream wait for the work the
  * handle still has in flight on the previous one and for the world pool's side streams, then carries on there.  Two
