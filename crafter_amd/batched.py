@@ -395,6 +395,54 @@ class BatchedEnv:
     self._keep = mask
     return out
 
+  # ------------------------------------------------------------------ symbolic observation (include/crafter_hip.h crafter_symbolic)
+  _OBJECT_CLASSES = ('player', 'cow', 'zombie', 'skeleton', 'arrow', 'plant')   # env.py:47-49, types.hpp T_*
+
+  @property
+  def symbolic_shape(self):
+    """((2, gw, gh), (n_items + 4,)): the per-env shapes of symbolic()'s pair."""
+    return (2, int(self.cfg.local_gw), int(self.cfg.local_gh)), (len(self.item_names) + 4,)
+
+  @property
+  def symbolic_names(self):
+    """{'classes': names indexed by the plane-0 id ('none', the materials, then player ... plant), 'stats': the column names
+    of stats}."""
+    return {'classes': ['none'] + list(self.rules['materials']) + list(self._OBJECT_CLASSES),
+            'stats': list(self.item_names) + ['facing_x', 'facing_y', 'sleeping', 'daylight']}
+
+  def symbolic(self, mask=None, out=None):
+    """The state self.obs depicts, as numbers: (local u8 [N, 2, gw, gh], stats f32 [N, n_items + 4]) on the device.
+    local[e, 0, x, y] is what info['semantic'] holds at world cell player.pos + (x, y) - (gw // 2, gh // 2) -- the cell the
+    frame shows there (engine.py:155-187) -- and 0 outside the world; local[e, 1, x, y] is the sprite variant of the object on
+    it (player 1 left, 2 right, 3 up, 4 down, 5 sleeping; arrow 1 .. 4; ripe plant 1; else 0).  stats: the inventory in
+    item_names order, facing x / y, sleeping, daylight (symbolic_names).  After a step() that auto-reset an env the pair
+    describes the new episode's first state, after a rollout() the state behind its last step.  Read-only: unlike render()
+    it draws nothing from the envs' RNG; works whatever `render` and `semantic` were.  mask: rows with a zero byte are left
+    untouched.  out = (local, stats): contiguous device tensors of exactly those dtypes and shapes to write into."""
+    ls, ss = self.symbolic_shape
+    shapes = ((self.num_envs,) + ls, torch.uint8), ((self.num_envs,) + ss, torch.float32)
+    if out is None:
+      out = tuple(torch.zeros(shape, dtype=dt, device=self.device) for shape, dt in shapes)
+    else:
+      if len(out) != 2:
+        raise ValueError('out must be a pair (local, stats)')
+      for t, (shape, dt) in zip(out, shapes):
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dt and tuple(t.shape) == shape and
+                t.is_contiguous()):
+          raise ValueError(f'out tensor must be a contiguous {dt} tensor of shape {shape} on {self.device}')
+    mptr = None
+    if mask is not None:
+      mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+      if mask.numel() != self.num_envs:
+        raise ValueError(f'mask must have {self.num_envs} elements')
+      mptr = C.c_void_p(mask.data_ptr())
+    local, stats = out
+    with torch.cuda.device(self.device):
+      self._check(self._lib.crafter_symbolic(self._handle, mptr, C.c_void_p(local.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                             self._stream()))
+    self._keep = mask
+    return local, stats
+
   def info(self):
     """Device-tensor views of what the reference puts into ``info`` (env.py:108-115)."""
     o, r = self._off, self._rec_i32

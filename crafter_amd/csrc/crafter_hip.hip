@@ -21,6 +21,7 @@
 #include "dispatch_order.hpp"
 #include "env_copy.hpp"
 #include "env_kernels.hpp"
+#include "symbolic.hpp"
 #include "wave_gfx950.hpp"
 
 using namespace crafter;
@@ -400,6 +401,19 @@ crafter_render_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __r
   if (mask && !mask[env]) return;
   WaveGfx950<kStepThreads> w;
   render_body(w, smem, env, cfg, tb, st, out);
+}
+
+// crafter_symbolic (symbolic.hpp): one wave per env, kSymbolicEnvs envs per workgroup, each wave in its own LDS strip.  No
+// barrier: the waves of the batch tail and of masked rows leave at once.  MAP: the cell -> slot map is state (maps in global memory).
+template <int MAP>
+__global__ void __launch_bounds__(kSymbolicThreads)
+crafter_symbolic_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, uint8_t* __restrict__ local,
+                        float* __restrict__ stats, int strip_bytes) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  typedef WaveGfx950<kSymbolicThreads> WS;
+  WS w;
+  const int wave = WS::uni((int)(threadIdx.x >> 6));
+  symbolic_body<WS, MAP>(w, smem + wave * strip_bytes, (int)blockIdx.x * kSymbolicEnvs + wave, cfg, tb, st, mask, local, stats);
 }
 
 // Builds the renderer's static block once per table upload (one workgroup).
@@ -1490,6 +1504,26 @@ int crafter_render(crafter_handle* h, const uint8_t* mask, uint8_t* out, void* s
                      (hipStream_t)stream, h->cfg, h->tb, h->st, mask, out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_render launch", e);
+  return 0;
+}
+
+// The symbolic observation of the state as it stands on `stream` (symbolic.hpp).  Reads live rows only -- the pool's side
+// streams never write them -- so, like crafter_save_envs, it waits for no batch.
+int crafter_symbolic(crafter_handle* h, const uint8_t* mask, uint8_t* local, float* stats, void* stream) {
+  if (ready(h, "crafter_symbolic")) return 1;
+  if (!local && !stats) return 0;
+  const int lds = kSymbolicEnvs * symbolic_strip_bytes(h->cfg);
+  if (lds > 64 * 1024) return fail(h, "crafter_symbolic: the local view is too large for the kernel's LDS strips");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  const dim3 grid((unsigned)((h->cfg.num_envs + kSymbolicEnvs - 1) / kSymbolicEnvs)), block(kSymbolicThreads);
+  if (lds_layout(h->cfg).maps_in_lds)
+    hipLaunchKernelGGL(crafter_symbolic_kernel<0>, grid, block, lds, (hipStream_t)stream, h->cfg, h->tb, h->st, mask, local, stats,
+                       symbolic_strip_bytes(h->cfg));
+  else
+    hipLaunchKernelGGL(crafter_symbolic_kernel<1>, grid, block, lds, (hipStream_t)stream, h->cfg, h->tb, h->st, mask, local, stats,
+                       symbolic_strip_bytes(h->cfg));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_symbolic launch", e);
   return 0;
 }
 

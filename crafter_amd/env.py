@@ -179,3 +179,8 @@ class Env(BaseClass):
   def render(self, size=None):
     size = None if size is None else tuple(int(v) for v in (size if hasattr(size, '__len__') else (size, size)))
     return self._batch.render(size)[0].cpu().numpy()
+
+  def symbolic(self):
+    """BatchedEnv.symbolic() for this env: (local uint8 [2, gw, gh], stats float32 [n_items + 4]) as numpy arrays."""
+    local, stats = self._batch.symbolic()
+    return local[0].cpu().numpy(), stats[0].cpu().numpy()

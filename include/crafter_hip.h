@@ -210,6 +210,19 @@ int crafter_debug_set_dispatch_order(crafter_handle* h, const int32_t* order);
  * draws the night noise from each env's RNG again (engine.py:208-209). */
 int crafter_render(crafter_handle* h, const uint8_t* mask, uint8_t* out, void* stream);
 
+/* The symbolic observation of the state the frame depicts (no reference counterpart as a call; every value is the reference's),
+ * for masked envs (NULL: all; rows with a zero mask byte are left untouched).  Either output may be NULL.
+ *   local: uint8 [num_envs][2][local_gw][local_gh], indexed [env][plane][x][y].  Local cell (x, y) is world cell
+ *     player.pos + (x, y) - (local_gw / 2, local_gh / 2) (engine.py:155-187, LocalView).  Plane 0: the value info['semantic']
+ *     has there (engine.py:251-264, SemanticView: the material id, or n_materials + 1 + class index where an object stands),
+ *     0 outside the world.  Plane 1: the sprite variant of the object on the cell (objects.py:85-93, 361-367, 395-403) --
+ *     player 1 left, 2 right, 3 up, 4 down, 5 sleeping; arrow 1 .. 4 likewise; plant 1 if ripe (grown > 300); otherwise 0.
+ *   stats: float [num_envs][n_items + 4]: the inventory in item order (env.py:108-115), facing x, facing y, sleeping (0 / 1)
+ *     and the daylight of the env's step (env.py:135-139: the table's double rounded to float).
+ * Read-only: unlike crafter_render it draws nothing from the env's RNG and changes no byte of state.  Reads live rows only:
+ * no wait for the world pool.  Additive under ABI revision 7: a binding looks it up by name. */
+int crafter_symbolic(crafter_handle* h, const uint8_t* mask, uint8_t* local, float* stats, void* stream);
+
 /* Measurement aid (no reference counterpart): when enabled, crafter_step attaches HIP start / stop events to
  * its two kernels (hipExtLaunchKernelGGL: the kernels' own execution time on the launch stream, what a
  * profiler reports).  crafter_get_timing waits for the recorded events, returns the SUM of step-kernel and
