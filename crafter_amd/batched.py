@@ -158,11 +158,8 @@ class BatchedEnv:
     rec['mt_pos'] = abi.MT_N
     rec['nobj'] = 1
     self.state['rec'].copy_(torch.from_numpy(rec.view(np.uint8).reshape(self.num_envs, -1)))
-    ptrs = {k: v.data_ptr() for k, v in self.state.items()}
-    for name in ('semantic', 'prof') + state.POOL_BUFFERS:
-      ptrs.setdefault(name, None)
     self.terminal = self.state['terminal']
-    self._st = abi.StatePtrs(**ptrs)
+    self._st = self._state_ptrs()
     self._native.bind(self._st)
     n = self.num_envs
     self.obs = torch.zeros((n, cfg.size_h, cfg.size_w, 3), dtype=torch.uint8, device=self.device)
@@ -171,6 +168,30 @@ class BatchedEnv:
     self._rec_i32 = self.state['rec'].view(torch.int32)
     off = {name: abi.REC_DTYPE.fields[name][1] // 4 for name in abi.REC_DTYPE.names}
     self._off = off
+
+  def _state_ptrs(self):
+    """abi.StatePtrs over self.state (+ the phase-stamp buffer, if enable_phase_stamps made one)."""
+    ptrs = {k: v.data_ptr() for k, v in self.state.items()}
+    for name in ('semantic', 'prof') + state.POOL_BUFFERS:
+      ptrs.setdefault(name, None)
+    if getattr(self, '_prof', None) is not None:
+      ptrs['prof'] = self._prof.data_ptr()
+    return abi.StatePtrs(**ptrs)
+
+  def _mask(self, mask, check_len=False):
+    """-> (contiguous uint8 device tensor or None -- for the caller to keep alive --, its pointer or None)"""
+    if mask is None:
+      return None, None
+    mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+    if check_len and mask.numel() != self.num_envs:
+      raise ValueError(f'mask must have {self.num_envs} elements')
+    return mask, C.c_void_p(mask.data_ptr())
+
+  def _actions(self, actions):
+    """-> contiguous int32 device tensor"""
+    if not (torch.is_tensor(actions) and actions.dtype == torch.int32 and actions.is_cuda):
+      actions = torch.as_tensor(actions, device=self.device).to(torch.int32)
+    return actions.contiguous()
 
   def __del__(self):
     try:
@@ -266,12 +287,7 @@ class BatchedEnv:
         if name in self.state:
           self.state[name].zero_()
       torch.cuda.synchronize(self.device)
-      ptrs = {k: v.data_ptr() for k, v in self.state.items()}
-      for name in ('semantic', 'prof') + state.POOL_BUFFERS:
-        ptrs.setdefault(name, None)
-      if getattr(self, '_prof', None) is not None:
-        ptrs['prof'] = self._prof.data_ptr()
-      self._st = abi.StatePtrs(**ptrs)
+      self._st = self._state_ptrs()
       native.bind(self._st)
     old.close()
     was_default = self.cfg.max_objects == 256
@@ -291,10 +307,7 @@ class BatchedEnv:
   # ------------------------------------------------------------------ Env API
   def reset(self, mask=None):
     """Env.reset() (env.py:70-81) for all envs, or those with a non-zero mask byte.  Returns obs."""
-    mptr = None
-    if mask is not None:
-      mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-      mptr = C.c_void_p(mask.data_ptr())
+    mask, mptr = self._mask(mask)
     with torch.cuda.device(self.device):
       self._check(self._lib.crafter_reset(self._handle, mptr, C.c_void_p(self.obs.data_ptr()), self._stream()))
     self._keep = mask
@@ -307,9 +320,7 @@ class BatchedEnv:
     of the next episode; done/reward still describe the finished step).
     out = (obs or None, reward, done): device tensors the kernels write instead of self.obs / self.reward /
     self.done (e.g. the send buffer of crafter_amd.dist.StepExchange); obs must be 16-byte aligned."""
-    if not (torch.is_tensor(actions) and actions.dtype == torch.int32 and actions.is_cuda):
-      actions = torch.as_tensor(actions, device=self.device).to(torch.int32)
-    actions = actions.contiguous()
+    actions = self._actions(actions)
     obs, reward, done = self.obs, self.reward, self.done
     if out is not None:
       obs = obs if out[0] is None else out[0]
@@ -330,9 +341,7 @@ class BatchedEnv:
     (obs u8[T,N,H,W,3] or None, reward f32[T,N], done u8[T,N]) -- bit-identical to T calls of step(), faster because an env
     starts its step t + 1 without waiting for every other env's step t (crafter_step_n).  out = (obs or None, reward,
     done): tensors of those shapes to write into.  self.obs / self.reward / self.done are NOT updated; the state is."""
-    if not (torch.is_tensor(actions) and actions.dtype == torch.int32 and actions.is_cuda):
-      actions = torch.as_tensor(actions, device=self.device).to(torch.int32)
-    actions = actions.contiguous()
+    actions = self._actions(actions)
     if actions.dim() != 2 or actions.shape[1] != self.num_envs or actions.shape[0] < 1:
       raise ValueError(f'actions must have shape [T, {self.num_envs}]')
     T = int(actions.shape[0])
@@ -386,10 +395,7 @@ class BatchedEnv:
     h = self._native if size is None else self._render_handle(size)
     shape = (self.num_envs, h.cfg.size_h, h.cfg.size_w, 3)
     out = torch.zeros(shape, dtype=torch.uint8, device=self.device) if out is None else out
-    mptr = None
-    if mask is not None:
-      mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-      mptr = C.c_void_p(mask.data_ptr())
+    mask, mptr = self._mask(mask)
     with torch.cuda.device(self.device):
       h.check(self._lib.crafter_render(h.ptr, mptr, C.c_void_p(out.data_ptr()), self._stream()))
     self._keep = mask
@@ -430,12 +436,7 @@ class BatchedEnv:
         if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dt and tuple(t.shape) == shape and
                 t.is_contiguous()):
           raise ValueError(f'out tensor must be a contiguous {dt} tensor of shape {shape} on {self.device}')
-    mptr = None
-    if mask is not None:
-      mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-      if mask.numel() != self.num_envs:
-        raise ValueError(f'mask must have {self.num_envs} elements')
-      mptr = C.c_void_p(mask.data_ptr())
+    mask, mptr = self._mask(mask, check_len=True)
     local, stats = out
     with torch.cuda.device(self.device):
       self._check(self._lib.crafter_symbolic(self._handle, mptr, C.c_void_p(local.data_ptr()), C.c_void_p(stats.data_ptr()),

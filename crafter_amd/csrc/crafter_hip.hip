@@ -21,6 +21,7 @@
 #include "dispatch_order.hpp"
 #include "env_copy.hpp"
 #include "env_kernels.hpp"
+#include "launch_plan.hpp"
 #include "symbolic.hpp"
 #include "wave_gfx950.hpp"
 
@@ -99,15 +100,9 @@ static_assert(cabi::CRAFTER_ST_BAD_COPY == ST_BAD_COPY && cabi::CRAFTER_ST_POOL_
 
 namespace {
 
-constexpr int kStepThreads = 256;    // step / render workgroup (compile-time: see WaveGfx950)
-constexpr int kResetThreads = 1024;  // reset / generation workgroup
+constexpr int kResetThreads = 1024;  // reset / generation workgroup (kStepThreads, kRequeueThreads: crafter_rollout.hpp)
 constexpr int kRequeueGrid = 256;
 constexpr int kRequeueGridPooled = 8;
-constexpr int kEarlyMinEnvs = 8 * 256;   // crafter_step_early_kernel from this many envs on (same-box A/B, profiles/r6_early_frame_ab.txt: 1536 envs -1.0 %, 2048 / 3072 +0.3 %, 4096 +0.1 ... +1.0 %, 8192 +1.2 %)
-constexpr int kOrderMinEnvs = 5 * 256;   // the dispatch order can only matter when a launch has more workgroups than the chip holds at once (5 per CU)
-constexpr int kRequeueThreads = 256;   // inline regeneration (rare): sized like a step workgroup, NOT like crafter_reset_kernel -- a
-                                       // 1024-thread workgroup needs a CU with all registers free, and with the world pool's kernels
-                                       // resident next to the step kernel even the EMPTY queue check would wait for one (measured: 32 us / step)
 constexpr int kGenSeedThreads = 64;       // world pool: seeding, one wave per world
 constexpr int kGenClassifyThreads = 256;  // terrain classification, four waves per world
 constexpr int kGenResolveThreads = 64;    // ordered draws, one wave per world
@@ -177,13 +172,10 @@ crafter_step_early_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32
   step_body<WS, 1, 1, uint8_t>(w, smem, env, cfg, tb, st, actions, obs, reward, done, ctl);
 }
 
-// The default instance for batches of at most two envs per CU (kWideMaxEnvs -- one GPU's share of configs[2]): 512 threads
-// per env.  A launch of so few envs lasts as long as its slowest env's step, most of the CUs' wave slots are empty, and the
-// frame is drawn by eight waves instead of four.  Same body, same LDS layout.  Measured (profiles/r4zy_wide_ab.txt): kernel
-// 27.8 -> 26.3 us at 512 envs (+4.8 % env-steps/s), +5 % at 256; at 768 envs -5 %, at 1024 -18 % (the frame's phases are
-// barrier to barrier: eight waves shorten them far less than they crowd a CU that holds three or four envs).
+// The default instance for batches of at most two envs per CU (launch_plan.hpp kWideMaxEnvs -- one GPU's share of configs[2]):
+// 512 threads per env.  A launch of so few envs lasts as long as its slowest env's step, most of the CUs' wave slots are empty,
+// and the frame is drawn by eight waves instead of four.  Same body, same LDS layout.
 constexpr int kWideThreads = 512;
-constexpr int kWideMaxEnvs = 2 * 256;
 __global__ void __launch_bounds__(kWideThreads, 6)
 crafter_step_wide_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ actions,
                          uint8_t* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done, StepCtl ctl) {
@@ -519,22 +511,14 @@ struct crafter_handle {
   bool have_state = false;
   std::vector<void*> owned;   // device allocations of the handle (tables)
   std::string shared_block_key;   // its entry in g_blocks (the renderer's derived tables), empty: none
-  int lds_bytes = 0;
-  int reset_lds_bytes = 0;
-  int step_lds_bytes = 0;   // the default-geometry step kernel keeps one-byte slot ids (env_kernels.hpp lds_layout); worlds whose maps
-                            // stay in HBM step in big_layout
-  bool default_rules = false;   // the uploaded rules are byte-identical to kDefaultRules
+  LaunchPlan plan;   // which step / rollout instance, in how much LDS (launch_plan.hpp): crafter_create, again in crafter_upload_tables
   int gen_resolve_lds_bytes = 0;
-  int split = -1;                         // the default instance steps as rules kernel (+ frame kernel): -1 = when no frame is drawn
-                                          // (with frames the fused step kernel is faster at every batch size measured: round 3,
-                                          // 4096 envs: fused 55.4 M, split pair 42-43 M, overlapped pair 31.5 M env-steps/s),
-                                          // CRAFTER_SPLIT=0 / 1 = never / always
-  int rules_lds_bytes = 0, frame_lds_bytes = 0;
+  int split = -1;                         // CRAFTER_SPLIT=0 / 1: the default instance never / always steps as rules kernel (+ frame kernel);
+                                          // -1: when no frame is drawn (launch_plan.hpp choose_step)
   int requeue_grid = kRequeueGridPooled;  // CRAFTER_REQUEUE_GRID (A/B): workgroups of the inline-regeneration kernel while the pool runs
   int gen_lag = kGenLag;                  // CRAFTER_GEN_LAG (A/B): back-pressure distance in batches, 1 .. kGenRing - 2
   int classify_grid = kGenClassifyGrid;   // CRAFTER_GEN_CLASSIFY_GRID: workgroups of the classification kernel (A/B)
   int classify_grid_step = kGenClassifyGrid;   // ... of a batch launched behind a closed-loop step (kGenClassifyGridStep for the default geometry)
-  int gen_lds_bytes = 0;   // the generation kernel never draws: no renderer region (4 step workgroups + 1 generator per CU)
   long long steps = 0;
   std::string err;
   // world pool (asynchronous generation on a side stream)
@@ -556,7 +540,6 @@ struct crafter_handle {
   uint64_t ordered_launches = 0;
   const int32_t* order_override = nullptr;   // diagnostics: crafter_debug_set_dispatch_order
   int lds_pad = 0;                        // CRAFTER_LDS_PAD
-  bool lds_pad_given = false;
   int rollout_order = 1;                  // CRAFTER_ROLLOUT_ORDER=0 (A/B): rollout launches in arrival order
   int rollout_lds_pad = 0;                // CRAFTER_ROLLOUT_LDS_PAD (A/B): extra LDS per workgroup of crafter_rollout_kernel<1, 1, 1> (26,872 B: six per CU)
   int32_t* stalled_at = nullptr;          // crafter_step_n: per env, the step of the call it stopped at for want of a world (-1: none)
@@ -610,6 +593,21 @@ static int hip_fail(crafter_handle* h, const char* what, hipError_t e) {
   return fail(h, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// The three kernels of generation batch `seq` over request segment `seg`, for the plan's GEO
+template <int GEO>
+static void launch_generation(crafter_handle* h, hipStream_t side, dim3 gs, dim3 gc, int seg, uint32_t seq, int prio) {
+  hipLaunchKernelGGL(crafter_gen_seed_kernel<GEO>, gs, dim3(kGenSeedThreads), kGenSeedLds, side, h->cfg, h->tb, h->st, seg, prio);
+  hipLaunchKernelGGL(crafter_gen_classify_kernel<GEO>, gc, dim3(kGenClassifyThreads), gen_classify_lds_bytes(h->cfg), side, h->cfg, h->tb, h->st, seg, h->gen_classify_prio);
+  hipLaunchKernelGGL(crafter_gen_resolve_kernel<GEO>, gs, dim3(kGenResolveThreads), h->gen_resolve_lds_bytes, side, h->cfg, h->tb,
+                     h->st, seg, seq, prio);
+}
+#ifdef CRAFTER_PROBES
+template <int GEO>
+static void launch_generation_stamp(crafter_handle* h, hipStream_t side, int seg, uint32_t seq) {
+  hipLaunchKernelGGL(crafter_gen_stamp_kernel<GEO>, dim3(64), dim3(kStepThreads), 0, side, h->cfg, h->tb, h->st, seg, seq);
+}
+#endif
+
 extern "C" {
 
 void crafter_struct_sizes(int32_t out[6]) {
@@ -641,14 +639,7 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
     return fail(nullptr, "crafter_create: no HIP device visible (this library has no CPU path)");
   crafter_handle* h = new crafter_handle();
   h->cfg = c;
-  h->lds_bytes = lds_layout(c).total;
-  h->reset_lds_bytes = big_reset_layout(c).total;   // Env.reset / regeneration kernels (= lds_bytes unless the maps stay in HBM)
-  h->step_lds_bytes = is_default_geometry(c) ? lds_layout(c, 1).total : !lds_layout(c).maps_in_lds ? big_layout(c).total : h->lds_bytes;
-  if (const char* pad = probe_env("CRAFTER_LDS_PAD")) {   // occupancy experiments: unused extra LDS per workgroup
-    h->lds_pad = atoi(pad) > 0 ? atoi(pad) : 0;
-    h->lds_pad_given = true;
-  }
-  h->step_lds_bytes += h->lds_pad;
+  if (const char* pad = probe_env("CRAFTER_LDS_PAD")) h->lds_pad = atoi(pad) > 0 ? atoi(pad) : 0;   // occupancy experiments: unused extra LDS per workgroup
   if (const char* v = probe_env("CRAFTER_ROLLOUT_ORDER")) h->rollout_order = atoi(v) != 0;
   if (const char* v = probe_env("CRAFTER_FOLD_MAIN_EVENT")) h->fold_main_event = atoi(v) != 0;
   if (const char* v = probe_env("CRAFTER_GEN_SERIAL_PRIO")) h->gen_serial_prio = atoi(v);
@@ -658,7 +649,7 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
   if (const char* v = probe_env("CRAFTER_PROBE_OCCUPY_BIG")) h->probe_big = atoi(v);
   if (const char* v = probe_env("CRAFTER_PROBE_OCCUPY")) sscanf(v, "%d,%d,%d,%d", &h->probe_worlds, &h->probe_us[0], &h->probe_us[1], &h->probe_us[2]);
   if (const char* pad = probe_env("CRAFTER_ROLLOUT_LDS_PAD")) h->rollout_lds_pad = atoi(pad) > 0 ? atoi(pad) : 0;   // ... of the resident rollout kernel
-  h->gen_lds_bytes = big_reset_layout(c).total_no_render;   // fused generation appended to crafter_reset_kernel runs in that kernel's LDS
+  h->plan = launch_plan(c, false, h->lds_pad, h->rollout_lds_pad);   // (the rules are not known yet)
   h->gen_resolve_lds_bytes = gen_resolve_layout(c).total;
   if (const char* v = probe_env("CRAFTER_GEN_LAG")) h->gen_lag = atoi(v) >= 1 && atoi(v) <= kGenRing - 2 ? atoi(v) : kGenLag;
   if (const char* v = getenv("CRAFTER_SPLIT")) h->split = atoi(v) < 0 ? -1 : atoi(v) != 0 ? 1 : 0;
@@ -668,11 +659,11 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
   if (const char* v = probe_env("CRAFTER_REQUEUE_GRID")) h->requeue_grid = atoi(v) >= 1 && atoi(v) <= kRequeueGrid ? atoi(v) : kRequeueGridPooled;
   // large worlds (maps in HBM): two classification workgroups per CU -- their step workgroups leave the registers, and a batch
   // is sixteen times the cells (8192 x 256x256, r4i: 256 / 512 / 1024 workgroups = 9.18 / 10.14 / 9.16 M env-steps/s)
-  if (!lds_layout(c).maps_in_lds) h->classify_grid = 2 * kGenClassifyGrid;
-  h->classify_grid_step = is_default_geometry(c) ? kGenClassifyGridStep : h->classify_grid;
+  if (!h->plan.maps_in_lds) h->classify_grid = 2 * kGenClassifyGrid;
+  h->classify_grid_step = h->plan.gen_geo ? kGenClassifyGridStep : h->classify_grid;
   if (const char* v = probe_env("CRAFTER_GEN_CLASSIFY_GRID")) h->classify_grid = h->classify_grid_step = atoi(v) > 0 ? atoi(v) : h->classify_grid;
-  if (h->lds_bytes > kMaxLds) {
-    std::string msg = "crafter_create: one environment needs " + std::to_string(h->lds_bytes) +
+  if (h->plan.render_lds > kMaxLds) {
+    std::string msg = "crafter_create: one environment needs " + std::to_string(h->plan.render_lds) +
                       " B of LDS (> 160 KiB): area / max_objects too large for the LDS-resident kernels";
     delete h;
     return fail(nullptr, msg);
@@ -682,21 +673,26 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
     return fail(nullptr, "crafter_create: workgroup sizes are fixed in this build (step_threads 0 or " +
                              std::to_string(kStepThreads) + ", reset_threads 0 or " + std::to_string(kResetThreads) + ")");
   }
-  if (h->lds_bytes > 64 * 1024) {   // large worlds only: the generic instances (the default geometry needs 31 KB)
-    const void* big[] = {(const void*)crafter_step_kernel<0, 0, 0>, (const void*)crafter_step_kernel<0, 2, 1>, (const void*)crafter_step_kernel<1, 0, 0>,
-                         (const void*)crafter_reset_kernel,         (const void*)crafter_gen_resolve_kernel<0>,
-                         (const void*)crafter_requeue_reset_kernel, (const void*)crafter_render_kernel};
-    hipError_t er = rollout_allow_lds(h->lds_bytes);   // the rollout kernels live in crafter_rollout.hip
+  if (h->plan.opt_in_lds) {   // large worlds only: the generic instances (the default geometry needs 33 KB)
+    std::vector<const void*> big;
+#define CRAFTER_X(id, LM, GEO, RUL) \
+    if constexpr (GEO != 1) big.push_back((const void*)crafter_step_kernel<LM, GEO, RUL>);
+    CRAFTER_STEP_INSTANCES(CRAFTER_X)
+#undef CRAFTER_X
+    for (const void* f : {(const void*)crafter_reset_kernel, (const void*)crafter_gen_resolve_kernel<0>,
+                          (const void*)crafter_requeue_reset_kernel, (const void*)crafter_render_kernel})
+      big.push_back(f);
+    hipError_t er = rollout_allow_lds(h->plan.render_lds);   // the rollout kernels live in crafter_rollout.hip
     if (er != hipSuccess) {
       std::string msg = std::string("crafter_create: hipFuncSetAttribute(rollout kernels): ") + hipGetErrorString(er);
       delete h;
       return fail(nullptr, msg);
     }
     for (const void* f : big) {
-      hipError_t ea = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes);
+      hipError_t ea = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, h->plan.render_lds);
       if (ea != hipSuccess) {
         std::string msg = std::string("crafter_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize, ") +
-                          std::to_string(h->lds_bytes) + "): " + hipGetErrorString(ea);
+                          std::to_string(h->plan.render_lds) + "): " + hipGetErrorString(ea);
         delete h;
         return fail(nullptr, msg);
       }
@@ -704,9 +700,7 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
   }
   {   // dispatch order (see crafter_handle::order).  CRAFTER_ORDER=0 / 1: never / whenever possible (A/B)
     const char* v = getenv("CRAFTER_ORDER");
-    int want = v ? atoi(v) : -1;
-    bool pays = c.num_envs > kOrderMinEnvs;
-    if (c.num_envs <= 64 * kStepThreads && (want > 0 || (want < 0 && pays))) {
+    if (keeps_dispatch_order(c.num_envs, v ? atoi(v) : -1)) {
       hipError_t ea = hipMalloc((void**)&h->order, 2 * (size_t)c.num_envs * sizeof(int32_t));
       if (ea == hipSuccess) ea = hipMalloc((void**)&h->next_step, (size_t)c.num_envs * sizeof(int32_t));
       if (ea == hipSuccess) ea = hipMemset(h->next_step, 0, (size_t)c.num_envs * sizeof(int32_t));
@@ -810,7 +804,7 @@ int crafter_upload_tables(crafter_handle* h, const crafter_host_tables* t) {
     return fail(h, "crafter_upload_tables: the renderer's row table holds " + std::to_string(kTileRows - 1) + " materials (render.hpp kTileRows)");
   TablePtrs& tb = h->tb;
   if (upload(h, t->rules, sizeof(Rules), (const void**)&tb.rules)) return 1;
-  h->default_rules = memcmp(t->rules, &kDefaultRules, sizeof(Rules)) == 0;
+  const bool default_rules = is_default_rules(*r);
   if (upload(h, t->atlas, t->atlas_bytes, (const void**)&tb.atlas)) return 1;
   if (upload(h, t->tex_tile, sizeof(int32_t) * t->n_tex_tile, (const void**)&tb.tex_tile)) return 1;
   if (upload(h, t->tex_icon, sizeof(int32_t) * t->n_tex_icon, (const void**)&tb.tex_icon)) return 1;
@@ -826,27 +820,17 @@ int crafter_upload_tables(crafter_handle* h, const crafter_host_tables* t) {
     uint64_t hash = 14695981039346656037ull;
     const int32_t geo[] = {c.unit_x, c.unit_y, c.local_gw, c.local_gh, c.item_gw, c.item_gh, c.size_w, c.size_h, c.icon_w, c.icon_h,
                            c.digit_w, c.digit_h, c.n_daylight, r->n_items, r->n_materials};
-    hash = fnv1a(hash, geo, sizeof(geo));
-    hash = fnv1a(hash, t->atlas, t->atlas_bytes);
-    hash = fnv1a(hash, t->tex_tile, sizeof(int32_t) * t->n_tex_tile);
-    hash = fnv1a(hash, t->tex_icon, sizeof(int32_t) * t->n_tex_icon);
-    hash = fnv1a(hash, t->tex_digit, sizeof(int32_t) * t->n_tex_digit);
-    hash = fnv1a(hash, t->tex_alpha, t->n_tex_alpha);
-    hash = fnv1a(hash, t->item_pos, sizeof(int32_t) * t->n_item_pos);
-    hash = fnv1a(hash, t->daylight, sizeof(double) * t->n_daylight);
-    hash = fnv1a(hash, t->vignette, sizeof(double) * t->n_vignette);
-    hash = fnv1a(hash, t->unit255, sizeof(float) * t->n_unit255);
+    const struct { const void* p; size_t n; } spans[] = {
+        {geo, sizeof(geo)}, {t->atlas, t->atlas_bytes}, {t->tex_tile, sizeof(int32_t) * t->n_tex_tile},
+        {t->tex_icon, sizeof(int32_t) * t->n_tex_icon}, {t->tex_digit, sizeof(int32_t) * t->n_tex_digit},
+        {t->tex_alpha, (size_t)t->n_tex_alpha}, {t->item_pos, sizeof(int32_t) * t->n_item_pos},
+        {t->daylight, sizeof(double) * t->n_daylight}, {t->vignette, sizeof(double) * t->n_vignette},
+        {t->unit255, sizeof(float) * t->n_unit255}};
     uint64_t hash2 = 0x243f6a8885a308d3ull;
-    hash2 = mix64(hash2, geo, sizeof(geo));
-    hash2 = mix64(hash2, t->atlas, t->atlas_bytes);
-    hash2 = mix64(hash2, t->tex_tile, sizeof(int32_t) * t->n_tex_tile);
-    hash2 = mix64(hash2, t->tex_icon, sizeof(int32_t) * t->n_tex_icon);
-    hash2 = mix64(hash2, t->tex_digit, sizeof(int32_t) * t->n_tex_digit);
-    hash2 = mix64(hash2, t->tex_alpha, t->n_tex_alpha);
-    hash2 = mix64(hash2, t->item_pos, sizeof(int32_t) * t->n_item_pos);
-    hash2 = mix64(hash2, t->daylight, sizeof(double) * t->n_daylight);
-    hash2 = mix64(hash2, t->vignette, sizeof(double) * t->n_vignette);
-    hash2 = mix64(hash2, t->unit255, sizeof(float) * t->n_unit255);
+    for (const auto& sp : spans) {
+      hash = fnv1a(hash, sp.p, sp.n);
+      hash2 = mix64(hash2, sp.p, sp.n);
+    }
     size_t bytes = (size_t)render_static_total_bytes(c);
     std::string key = std::to_string(dev) + "|" + std::to_string(hash) + "|" + std::to_string(hash2) + "|" + std::to_string(bytes);
     std::lock_guard<std::mutex> lock(g_blocks_mutex);
@@ -869,13 +853,7 @@ int crafter_upload_tables(crafter_handle* h, const crafter_host_tables* t) {
     h->shared_block_key = key;
     tb.render_static = (const uint8_t*)it->second.ptr;
   }
-  // The fused instances that run the compiled-in rules stage none: their layout is 280 bytes shorter (lds_layout with_rules
-  // false) -- 26,872 B, which lets a SIXTH workgroup onto a CU (round 5; the step kernel's 61 VGPRs allow seven).  Same-box
-  // A/B of the closed loop, CRAFTER_LDS_PAD=280 (five) against 0 (six): step kernel 60.9 -> 58.6 us, env-steps/s 62.07 -> 62.23 M
-  // at 4096 envs, equal at 1024, no inline regeneration either way (profiles/r5_closed_occupancy_ab.txt): the kernel is
-  // shorter, the world pool's kernels get their turn in the gaps instead of beside it.
-  if (is_default_geometry(c) && h->default_rules)
-    h->step_lds_bytes = lds_layout(c, 1, false, false).total + h->lds_pad;
+  h->plan = launch_plan(c, default_rules, h->lds_pad, h->rollout_lds_pad);   // the rules are known: the instance may be a compiled-in one
   h->have_tables = true;
   return 0;
 }
@@ -893,7 +871,7 @@ int crafter_extend_daylight(crafter_handle* h, const double* daylight, int32_t n
   const void* d = nullptr;
   if (upload(h, daylight, sizeof(double) * (size_t)n, &d)) return 1;
   h->tb.daylight = (const double*)d;
-  h->cfg.n_daylight = n;
+  h->cfg.n_daylight = n;   // (no part of the launch plan: launch_plan.hpp)
   return 0;
 }
 
@@ -913,17 +891,11 @@ int crafter_bind_state(crafter_handle* h, const crafter_state_ptrs* state) {
   return 0;
 }
 
-int32_t crafter_lds_bytes(const crafter_handle* h) { return h ? h->step_lds_bytes : -1; }
+int32_t crafter_lds_bytes(const crafter_handle* h) { return h ? h->plan.step_lds : -1; }
 
-int32_t crafter_slot_map_derived(const crafter_handle* h) { return h ? lds_layout(h->cfg).maps_in_lds : -1; }
+int32_t crafter_slot_map_derived(const crafter_handle* h) { return h ? h->plan.maps_in_lds : -1; }
 
-int32_t crafter_step_instance(const crafter_handle* h) {
-  if (!h) return -1;
-  int lm = lds_layout(h->cfg).maps_in_lds ? 1 : 0, geo = is_default_geometry(h->cfg) ? 1 : 0;
-  int rul = (geo && h->have_tables && h->default_rules) ? 1 : 0;
-  if (!lm && is_default_view(h->cfg) && h->have_tables && h->default_rules) return 8 + 1;   // crafter_step_kernel<0, 2, 1>
-  return lm * 4 + geo * 2 + rul;
-}
+int32_t crafter_step_instance(const crafter_handle* h) { return h ? h->plan.instance : -1; }
 
 static int ready(crafter_handle* h, const char* who) {
   if (!h) return fail(nullptr, std::string(who) + ": null handle");
@@ -953,8 +925,7 @@ static void pool_adopt_stream(crafter_handle* h, hipStream_t stream) {
       // that one is waiting for more)
       hipError_t ew = hipStreamWaitEvent(stream, h->ev_gen[s % kGenRing], 0);
       if (ew != hipSuccess) {
-        h->pool_failed = true;
-        h->pool_err = std::string("world pool disabled (hipStreamWaitEvent(new launch stream): ") + hipGetErrorString(ew) + "); finished envs regenerate inline";
+        pool_fail(h, "hipStreamWaitEvent(new launch stream)", ew);
         h->safe_seq = h->polled_seq;
         break;
       }
@@ -1055,23 +1026,16 @@ static void pool_schedule(crafter_handle* h, hipStream_t main, int steps = 1, bo
         hipLaunchKernelGGL(crafter_gen_occupy_kernel<0>, dim3(ws), dim3(kGenResolveThreads), l2, side, h->probe_us[2], worlds, (uint32_t*)nullptr);
       }
     }
-    if (is_default_geometry(h->cfg))
-      hipLaunchKernelGGL(crafter_gen_stamp_kernel<1>, dim3(64), dim3(kStepThreads), 0, side, h->cfg, h->tb, h->st, seg, seq);
+    if (h->plan.gen_geo)
+      launch_generation_stamp<1>(h, side, seg, seq);
     else
-      hipLaunchKernelGGL(crafter_gen_stamp_kernel<0>, dim3(64), dim3(kStepThreads), 0, side, h->cfg, h->tb, h->st, seg, seq);
+      launch_generation_stamp<0>(h, side, seg, seq);
   } else
 #endif
-  if (is_default_geometry(h->cfg)) {
-    hipLaunchKernelGGL(crafter_gen_seed_kernel<1>, gs, dim3(kGenSeedThreads), kGenSeedLds, side, h->cfg, h->tb, h->st, seg, prio);
-    hipLaunchKernelGGL(crafter_gen_classify_kernel<1>, gc, dim3(kGenClassifyThreads), gen_classify_lds_bytes(h->cfg), side, h->cfg, h->tb, h->st, seg, h->gen_classify_prio);
-    hipLaunchKernelGGL(crafter_gen_resolve_kernel<1>, gs, dim3(kGenResolveThreads), h->gen_resolve_lds_bytes, side, h->cfg, h->tb,
-                       h->st, seg, seq, prio);
-  } else {
-    hipLaunchKernelGGL(crafter_gen_seed_kernel<0>, gs, dim3(kGenSeedThreads), kGenSeedLds, side, h->cfg, h->tb, h->st, seg, prio);
-    hipLaunchKernelGGL(crafter_gen_classify_kernel<0>, gc, dim3(kGenClassifyThreads), gen_classify_lds_bytes(h->cfg), side, h->cfg, h->tb, h->st, seg, h->gen_classify_prio);
-    hipLaunchKernelGGL(crafter_gen_resolve_kernel<0>, gs, dim3(kGenResolveThreads), h->gen_resolve_lds_bytes, side, h->cfg, h->tb,
-                       h->st, seg, seq, prio);
-  }
+  if (h->plan.gen_geo)
+    launch_generation<1>(h, side, gs, gc, seg, seq, prio);
+  else
+    launch_generation<0>(h, side, gs, gc, seg, seq, prio);
   e = hipGetLastError();
   if (e != hipSuccess) return pool_fail(h, "generation kernel launch", e);
   // from here on the batch exists: the sequence number is consumed even if a later call fails (its event would then
@@ -1085,6 +1049,15 @@ static void pool_schedule(crafter_handle* h, hipStream_t main, int steps = 1, bo
   if (e != hipSuccess) return pool_fail(h, "hipEventRecord(generation stream)", e);
 }
 
+// Orders `stream` behind every launched batch (hipStreamWaitEvent: the host does not block) and trusts them all.
+static void pool_wait_all(crafter_handle* h, hipStream_t stream, const char* what) {
+  for (uint32_t s = h->safe_seq + 1; s <= h->batches && !h->pool_failed; s++) {
+    hipError_t ew = hipStreamWaitEvent(stream, h->ev_gen[s % kGenRing], 0);
+    if (ew != hipSuccess) pool_fail(h, what, ew);
+  }
+  if (!h->pool_failed) h->safe_seq = h->batches;
+}
+
 int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* stream) {
   if (ready(h, "crafter_reset")) return 1;
   // The reset kernel generates the next episode's world into the env's pool entry itself (gen_one): it must not share
@@ -1092,17 +1065,8 @@ int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* st
   // k + 2 in such a batch, and k + 2 lives in the entry the kernel is about to write: ADVICE r2).  So the launch stream
   // is ordered behind every launched batch first -- no host wait -- and all of them are trusted from here on.
   if (adopt_stream(h, (hipStream_t)stream)) return 1;
-  if (h->pool && !h->pool_failed) {
-    for (uint32_t s = h->safe_seq + 1; s <= h->batches; s++) {
-      hipError_t ew = hipStreamWaitEvent((hipStream_t)stream, h->ev_gen[s % kGenRing], 0);
-      if (ew != hipSuccess) {
-        pool_fail(h, "hipStreamWaitEvent(reset)", ew);
-        break;
-      }
-    }
-    if (!h->pool_failed) h->safe_seq = h->batches;
-  }
-  hipLaunchKernelGGL(crafter_reset_kernel, dim3(h->cfg.num_envs), dim3(kResetThreads), h->reset_lds_bytes,
+  if (h->pool && !h->pool_failed) pool_wait_all(h, (hipStream_t)stream, "hipStreamWaitEvent(reset)");
+  hipLaunchKernelGGL(crafter_reset_kernel, dim3(h->cfg.num_envs), dim3(kResetThreads), h->plan.reset_lds,
                      (hipStream_t)stream, h->cfg, h->tb, h->st, mask, (h->pool && !h->pool_failed) ? h->gen_parity : -1, obs);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_reset launch", e);
@@ -1117,18 +1081,14 @@ int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* st
 static void pool_quiesce(crafter_handle* h, hipStream_t stream) {
   if (!h->pool || h->pool_failed) return;
   pool_schedule(h, stream, h->gen_period);
-  for (uint32_t s = h->safe_seq + 1; s <= h->batches && !h->pool_failed; s++) {
-    hipError_t ew = hipStreamWaitEvent(stream, h->ev_gen[s % kGenRing], 0);
-    if (ew != hipSuccess) pool_fail(h, "hipStreamWaitEvent(copy)", ew);
-  }
-  if (!h->pool_failed) h->safe_seq = h->batches;
+  pool_wait_all(h, stream, "hipStreamWaitEvent(copy)");
 }
 
 // The index check, then the copy (env_copy.hpp).  pool_rows: the pool is at rest and both sides are the bound state.
 static int launch_copy(crafter_handle* h, const char* who, int mode, const CopySide& a, const CopySide& b, const int32_t* sidx,
                        const int32_t* didx, int n, hipStream_t stream, bool pool_rows) {
   CopyPlan plan;
-  if (!make_copy_plan(plan, h->cfg, a, b, mode, !lds_layout(h->cfg).maps_in_lds, (size_t)h->cfg.size_w * h->cfg.size_h * 3, pool_rows))
+  if (!make_copy_plan(plan, h->cfg, a, b, mode, !h->plan.maps_in_lds, (size_t)h->cfg.size_w * h->cfg.size_h * 3, pool_rows))
     return fail(h, std::string(who) + ": too many buffers for one copy plan");
   if (!h->copy_mark) {
     hipError_t ea = hipMalloc((void**)&h->copy_mark, ((size_t)h->cfg.num_envs + 1) * sizeof(int32_t));
@@ -1157,7 +1117,7 @@ static int check_store(crafter_handle* h, const char* who, const crafter_state_p
   const StatePtrs& s = *store;
   if (!s.mat || !s.objs || !s.mt || !s.rec || !s.chunk_order || !s.chunk_seen || !s.census)
     return fail(h, std::string(who) + ": null store buffer");
-  if (!lds_layout(h->cfg).maps_in_lds && !s.objmap) return fail(h, std::string(who) + ": this world keeps its slot map in HBM: the store needs objmap");
+  if (!h->plan.maps_in_lds && !s.objmap) return fail(h, std::string(who) + ": this world keeps its slot map in HBM: the store needs objmap");
   if (s.pool_mat || s.pool_hdr || s.gen_q || s.gen_latest) return fail(h, std::string(who) + ": a store holds no pool buffers or queues");
   return 0;
 }
@@ -1204,16 +1164,6 @@ int crafter_load_envs(crafter_handle* h, const crafter_state_ptrs* store, int32_
   return launch_copy(h, "crafter_load_envs", COPY_LOAD, a, b, rows, idx, n, (hipStream_t)stream, false);
 }
 
-// A launch with start / stop events attached (timing mode: hipExtLaunchKernelGGL) or a plain one -- the plain launch is
-// the cheaper call on the host, which is what bounds small batches (tools/host_overhead.py).
-#define CRAFTER_LAUNCH(kernel, grid, block, lds, stream, start, stop, ...)                                          \
-  do {                                                                                                              \
-    if ((start) != nullptr || (stop) != nullptr)                                                                    \
-      hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, start, stop, 0, __VA_ARGS__);                         \
-    else                                                                                                            \
-      hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                            \
-  } while (0)
-
 static int requeue_grid(const crafter_handle* h, const StepCtl& ctl) {
   // With the world pool running the queue is all but always empty (0 of 68,684 resets in the benchmark): a handful of
   // workgroups finds that out faster than 256 (each needs a slot next to the resident generation workgroups).  Without
@@ -1222,7 +1172,7 @@ static int requeue_grid(const crafter_handle* h, const StepCtl& ctl) {
   return (ctl.gen_parity >= 0 && full > h->requeue_grid) ? h->requeue_grid : full;
 }
 static void launch_requeue(crafter_handle* h, const StepCtl& ctl, uint8_t* obs, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
-  CRAFTER_LAUNCH(crafter_requeue_reset_kernel, dim3(requeue_grid(h, ctl)), dim3(kRequeueThreads), h->reset_lds_bytes, stream, start, stop,
+  CRAFTER_LAUNCH(crafter_requeue_reset_kernel, dim3(requeue_grid(h, ctl)), dim3(kRequeueThreads), h->plan.reset_lds, stream, start, stop,
                         h->cfg, h->tb, h->st, ctl.parity, ctl.gen_parity, obs);
 }
 
@@ -1244,6 +1194,45 @@ static int need_night_px(crafter_handle* h, const char* who) {
   return 0;
 }
 
+// timing mode: start / stop events attached to the kernels themselves (hipExtLaunchKernelGGL), i.e. the
+// execution time a profiler reports, without the dispatch latency a hipEventRecord bracket would include
+static int timing_events(crafter_handle* h, hipEvent_t ev[4], const char* who) {
+  if (h->timing)
+    for (int i = 0; i < 4; i++) {
+      hipError_t ee = hipEventCreate(&ev[i]);
+      if (ee != hipSuccess) return hip_fail(h, who, ee);
+    }
+  return 0;
+}
+static void keep_timing_events(crafter_handle* h, hipEvent_t ev[4]) {
+  if (h->timing)
+    for (int i = 0; i < 4; i++) h->events.push_back(ev[i]);
+}
+
+// The dispatch order of an ordered launch (crafter_handle::order; one order for crafter_step and crafter_step_n): launch k
+// reads the half launch k - 1 built and builds the other.  The launch needs one block more: block 0 builds.
+static void set_dispatch_order(crafter_handle* h, StepCtl& ctl) {
+  uint64_t k = h->ordered_launches++;
+  ctl.order = k > 0 ? h->order + (size_t)(k & 1) * h->cfg.num_envs : nullptr;
+  if (h->order_override) ctl.order = h->order_override;
+  ctl.order_build = h->order + (size_t)((k + 1) & 1) * h->cfg.num_envs;
+  ctl.next_step = h->next_step;
+}
+
+// crafter_step_kernel<LM, GEO, RUL> of the plan's instance
+static void launch_step_fused(crafter_handle* h, dim3 grid, hipStream_t stream, hipEvent_t start, hipEvent_t stop, const int32_t* actions,
+                              uint8_t* obs, float* reward, uint8_t* done, const StepCtl& ctl) {
+  switch (h->plan.instance) {
+#define CRAFTER_X(id, LM, GEO, RUL)                                                                                              \
+    case id:                                                                                                                     \
+      CRAFTER_LAUNCH((crafter_step_kernel<LM, GEO, RUL>), grid, dim3(kStepThreads), h->plan.step_lds, stream, start, stop, h->cfg, \
+                     h->tb, h->st, actions, obs, reward, done, ctl);                                                             \
+      break;
+    CRAFTER_STEP_INSTANCES(CRAFTER_X)
+#undef CRAFTER_X
+  }
+}
+
 int crafter_step(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
                  void* stream) {
   if (ready(h, "crafter_step")) return 1;
@@ -1252,92 +1241,73 @@ int crafter_step(crafter_handle* h, const int32_t* actions, uint8_t* obs, float*
   StepCtl ctl;
   ctl.gen_parity = (h->pool && !h->pool_failed) ? h->gen_parity : -1;
   ctl.safe_seq = h->safe_seq;
-  // timing mode: start / stop events attached to the kernels themselves (hipExtLaunchKernelGGL), i.e. the
-  // execution time a profiler reports, without the dispatch latency a hipEventRecord bracket would include
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  dim3 grid_n(h->cfg.num_envs), block_s(kStepThreads);
-  bool frames = h->cfg.render_obs != 0 && obs != nullptr;
-  bool split = h->split < 0 ? !frames : h->split != 0;
-  bool requeue = h->cfg.auto_reset != 0;
-  bool pair = is_default_geometry(h->cfg) && h->default_rules && split;   // rules kernel (+ frame kernel) instead of the fused step kernel
-  bool ordered = h->order && !pair;
+  const bool frames = h->cfg.render_obs != 0 && obs != nullptr;
+  const bool requeue = h->cfg.auto_reset != 0;
+  const StepKernel kernel = choose_step(h->plan, h->cfg.num_envs, frames, h->order != nullptr, h->split, h->wide, h->early_frame);
+  const bool ordered = h->order && !is_split(kernel);   // (the wide kernel is only chosen where no order is kept)
   ctl.parity = (int)(h->steps++ & 1);   // (the reset_q halves alternate over the launches that use them)
-  ctl.early_frame = h->early_frame < 0 ? (h->cfg.num_envs >= kEarlyMinEnvs ? 1 : 0) : h->early_frame;
-  if (h->timing)
-    for (int i = 0; i < 4; i++) {
-      hipError_t ee = hipEventCreate(&ev[i]);
-      if (ee != hipSuccess) return hip_fail(h, "crafter_step: hipEventCreate (timing mode)", ee);
-    }
-  if (frames && !pair) {   // a fused step kernel draws: its night frames take their noise from states generated ahead
+  ctl.early_frame = step_early_frame(h->cfg.num_envs, h->early_frame);
+  if (timing_events(h, ev, "crafter_step: hipEventCreate (timing mode)")) return 1;
+  // the scratch the choice needs
+  if (frames && !is_split(kernel)) {   // a fused step kernel draws: its night frames take their noise from states generated ahead
     if (need_noise_raw(h, "crafter_step: noise scratch")) return 1;
     ctl.noise_raw = h->noise_raw;
   }
-  if (ordered) {
-    uint64_t k = h->ordered_launches++;
-    ctl.order = k > 0 ? h->order + (size_t)(k & 1) * h->cfg.num_envs : nullptr;
-    if (h->order_override) ctl.order = h->order_override;
-    ctl.order_build = h->order + (size_t)((k + 1) & 1) * h->cfg.num_envs;
-    ctl.next_step = h->next_step;
-    grid_n = dim3(h->cfg.num_envs + 1);   // block 0 builds the next launch's order
+  if (ordered) set_dispatch_order(h, ctl);
+  if (kernel == kStepRulesFrame && need_night_px(h, "crafter_step: frame kernel scratch")) return 1;
+  if (h->plan.night_px) {
+    if (frames && need_night_px(h, "crafter_step: night frame scratch")) return 1;
+    ctl.night_px = h->night_px;
   }
+  const dim3 grid_n(h->cfg.num_envs + (ordered ? 1 : 0)), block_s(kStepThreads);   // (ordered: block 0 builds the next launch's order)
   // The regeneration kernel (envs that finished and found no world in the pool: all but never any) only has to sit between
   // the rules of this step and the rules of the next.  In the split step it runs BESIDE the frame kernel, on the handle's own
   // stream -- the envs it regenerates and draws are exactly those the frame kernel skips -- so its launch and the look at
   // the (empty) queue cost the launch stream nothing.
   bool beside = false;
-  if (pair) {   // split step: rules at wave granularity, then the frames
-    if (frames && need_night_px(h, "crafter_step: frame kernel scratch")) return 1;
-    CRAFTER_LAUNCH(crafter_rules_kernel, grid_n, dim3(kRulesThreads), lane_layout(h->cfg).total, (hipStream_t)stream, ev[0],
-                          frames ? nullptr : ev[1], h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
-    if (frames && requeue && h->aux) {
-      hipError_t ea = hipEventRecord(h->ev_rules, (hipStream_t)stream);
-      if (ea == hipSuccess) ea = hipStreamWaitEvent(h->aux, h->ev_rules, 0);
-      if (ea != hipSuccess) return hip_fail(h, "crafter_step: fork to the regeneration stream", ea);
-      beside = true;
-      launch_requeue(h, ctl, obs, h->aux, ev[2], ev[3]);
-      ea = hipEventRecord(h->ev_requeue, h->aux);
-      if (ea != hipSuccess) return hip_fail(h, "crafter_step: hipEventRecord(regeneration stream)", ea);
-    }
-    if (frames)
+  switch (kernel) {
+    case kStepRules:   // split step: rules at wave granularity ...
+      CRAFTER_LAUNCH(crafter_rules_kernel, grid_n, dim3(kRulesThreads), lane_layout(h->cfg).total, (hipStream_t)stream, ev[0], ev[1],
+                     h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
+      break;
+    case kStepRulesFrame:   // ... then the frames
+      CRAFTER_LAUNCH(crafter_rules_kernel, grid_n, dim3(kRulesThreads), lane_layout(h->cfg).total, (hipStream_t)stream, ev[0], nullptr,
+                     h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
+      if (requeue && h->aux) {
+        hipError_t ea = hipEventRecord(h->ev_rules, (hipStream_t)stream);
+        if (ea == hipSuccess) ea = hipStreamWaitEvent(h->aux, h->ev_rules, 0);
+        if (ea != hipSuccess) return hip_fail(h, "crafter_step: fork to the regeneration stream", ea);
+        beside = true;
+        launch_requeue(h, ctl, obs, h->aux, ev[2], ev[3]);
+        ea = hipEventRecord(h->ev_requeue, h->aux);
+        if (ea != hipSuccess) return hip_fail(h, "crafter_step: hipEventRecord(regeneration stream)", ea);
+      }
       CRAFTER_LAUNCH(crafter_frame_kernel, grid_n, block_s, frame_layout(h->cfg).total, (hipStream_t)stream, nullptr, ev[1],
-                            h->cfg, h->tb, h->st, obs, h->night_px);
-    if (beside) {
-      hipError_t ea = hipStreamWaitEvent((hipStream_t)stream, h->ev_requeue, 0);
-      if (ea != hipSuccess) return hip_fail(h, "crafter_step: join of the regeneration stream", ea);
-    }
-  } else if (is_default_geometry(h->cfg) && h->default_rules && !ordered && frames &&
-             (h->wide < 0 ? h->cfg.num_envs <= kWideMaxEnvs : h->wide != 0)) {   // few envs: eight waves per env
-    CRAFTER_LAUNCH(crafter_step_wide_kernel, grid_n, dim3(kWideThreads), h->step_lds_bytes, (hipStream_t)stream, ev[0], ev[1],
-                          h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
-  } else if (is_default_geometry(h->cfg) && h->default_rules && frames && ctl.early_frame) {   // ... in batches larger than the chip holds at once
-    CRAFTER_LAUNCH(crafter_step_early_kernel, grid_n, block_s, h->step_lds_bytes, (hipStream_t)stream, ev[0], ev[1],
-                          h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
-  } else if (is_default_geometry(h->cfg) && h->default_rules) {   // crafter.Env() as everybody runs it
-    CRAFTER_LAUNCH((crafter_step_kernel<1, 1, 1>), grid_n, block_s, h->step_lds_bytes, (hipStream_t)stream, ev[0], ev[1],
-                          h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
-  } else if (is_default_geometry(h->cfg)) {                 // implies LDS-resident maps
-    CRAFTER_LAUNCH((crafter_step_kernel<1, 1, 0>), grid_n, block_s, h->step_lds_bytes, (hipStream_t)stream, ev[0], ev[1],
-                          h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
-  } else if (lds_layout(h->cfg).maps_in_lds) {
-    CRAFTER_LAUNCH((crafter_step_kernel<1, 0, 0>), grid_n, block_s, h->lds_bytes, (hipStream_t)stream, ev[0], ev[1],
-                          h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
-  } else {
-    if (frames && need_night_px(h, "crafter_step: night frame scratch")) return 1;
-    ctl.night_px = h->night_px;
-    if (is_default_view(h->cfg) && h->default_rules)   // BASELINE configs[3]: crafter.Env(area=(256, 256)) -- the default view and rules compiled in
-      CRAFTER_LAUNCH((crafter_step_kernel<0, 2, 1>), grid_n, block_s, h->step_lds_bytes, (hipStream_t)stream, ev[0], ev[1],
-                            h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
-    else
-      CRAFTER_LAUNCH((crafter_step_kernel<0, 0, 0>), grid_n, block_s, h->step_lds_bytes, (hipStream_t)stream, ev[0], ev[1],
-                            h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
+                     h->cfg, h->tb, h->st, obs, h->night_px);
+      if (beside) {
+        hipError_t ea = hipStreamWaitEvent((hipStream_t)stream, h->ev_requeue, 0);
+        if (ea != hipSuccess) return hip_fail(h, "crafter_step: join of the regeneration stream", ea);
+      }
+      break;
+    case kStepWide:   // few envs: eight waves per env
+      CRAFTER_LAUNCH(crafter_step_wide_kernel, grid_n, dim3(kWideThreads), h->plan.step_lds, (hipStream_t)stream, ev[0], ev[1],
+                     h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
+      break;
+    case kStepEarly:   // batches larger than the chip holds at once
+      CRAFTER_LAUNCH(crafter_step_early_kernel, grid_n, block_s, h->plan.step_lds, (hipStream_t)stream, ev[0], ev[1],
+                     h->cfg, h->tb, h->st, actions, obs, reward, done, ctl);
+      break;
+    case kStepFused:
+      launch_step_fused(h, grid_n, (hipStream_t)stream, ev[0], ev[1], actions, obs, reward, done, ctl);
+      break;
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_step launch", e);
   if (requeue && !beside) launch_requeue(h, ctl, obs, (hipStream_t)stream, ev[2], ev[3]);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_step (auto-reset) launch", e);
-  if (h->timing)
-    for (int i = 0; i < 4; i++) h->events.push_back(ev[i]);
+  keep_timing_events(h, ev);
   if (h->pool && !h->pool_failed) pool_schedule(h, (hipStream_t)stream);
   return 0;
 }
@@ -1396,7 +1366,6 @@ int crafter_step_n(crafter_handle* h, int32_t steps, const int32_t* actions, uin
   }
   const size_t n = (size_t)h->cfg.num_envs;
   const size_t obs_stride = n * (size_t)h->cfg.size_w * h->cfg.size_h * 3;
-  dim3 grid_n(h->cfg.num_envs), block_s(kStepThreads);
   bool requeue = h->cfg.auto_reset != 0;
   for (int done_steps = 0; done_steps < steps;) {
     int left = steps - done_steps;
@@ -1417,32 +1386,17 @@ int crafter_step_n(crafter_handle* h, int32_t steps, const int32_t* actions, uin
     RolloutArgs ra;
     ra.T = T; ra.obs_stride = obs_stride; ra.stalled_at = h->stalled_at;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (h->timing)
-      for (int i = 0; i < 4; i++) {
-        hipError_t ee = hipEventCreate(&ev[i]);
-        if (ee != hipSuccess) return hip_fail(h, "crafter_step_n: hipEventCreate (timing mode)", ee);
-      }
-    int instance = (is_default_geometry(h->cfg) && h->default_rules) ? 7 : is_default_geometry(h->cfg) ? 6 : lds_layout(h->cfg).maps_in_lds ? 4 : 0;
-    if (instance == 0 && is_default_view(h->cfg) && h->default_rules) instance = 9;   // (as crafter_step_kernel<0, 2, 1>)
+    if (timing_events(h, ev, "crafter_step_n: hipEventCreate (timing mode)")) return 1;
     if (o && h->cfg.render_obs) {
       if (need_noise_raw(h, "crafter_step_n: noise scratch")) return 1;
       ctl.noise_raw = h->noise_raw;
     }
-    if (h->order && h->rollout_order) {   // slow envs first, as in crafter_step (one order for both kinds of launch)
-      uint64_t k = h->ordered_launches++;
-      ctl.order = k > 0 ? h->order + (size_t)(k & 1) * h->cfg.num_envs : nullptr;
-      if (h->order_override) ctl.order = h->order_override;
-      ctl.order_build = h->order + (size_t)((k + 1) & 1) * h->cfg.num_envs;
-      ctl.next_step = h->next_step;
-    }
-    if (instance == 0 || instance == 9) {   // big_layout (as crafter_step_kernel<0, 0, 0>)
+    if (h->order && h->rollout_order) set_dispatch_order(h, ctl);   // slow envs first, as in crafter_step
+    if (h->plan.night_px) {   // big_layout
       if (o && h->cfg.render_obs && need_night_px(h, "crafter_step_n: night frame scratch")) return 1;
       ctl.night_px = h->night_px;
     }
-    // (the default instance keeps no staged rules in its resident layout)
-    size_t rollout_lds = instance == 7 ? (size_t)lds_layout(h->cfg, 1, false, false).total + (size_t)h->rollout_lds_pad
-                         : (instance == 6 || instance == 0 || instance == 9) ? (size_t)h->step_lds_bytes : (size_t)h->lds_bytes;
-    launch_rollout(instance, h->cfg.num_envs, rollout_lds, (hipStream_t)stream, ev[0], ev[1], h->cfg, h->tb, h->st,
+    launch_rollout(h->plan.instance, h->cfg.num_envs, (size_t)h->plan.rollout_lds, (hipStream_t)stream, ev[0], ev[1], h->cfg, h->tb, h->st,
                    a, o, r, d, ctl, ra);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(h, "crafter_step_n launch", e);
@@ -1450,12 +1404,11 @@ int crafter_step_n(crafter_handle* h, int32_t steps, const int32_t* actions, uin
     // own stop event)
     const bool batch_follows = pooled && requeue && !h->timing && h->fold_main_event && h->steps_since_gen + T >= h->gen_period;
     if (requeue)
-      launch_requeue_rollout(requeue_grid(h, ctl), h->lds_bytes, (hipStream_t)stream, ev[2], batch_follows ? h->ev_main : ev[3], h->cfg, h->tb,
+      launch_requeue_rollout(requeue_grid(h, ctl), (size_t)h->plan.render_lds, (hipStream_t)stream, ev[2], batch_follows ? h->ev_main : ev[3], h->cfg, h->tb,
                              h->st, a, o, r, d, ctl, ra);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(h, "crafter_step_n (auto-reset) launch", e);
-    if (h->timing)
-      for (int i = 0; i < 4; i++) h->events.push_back(ev[i]);
+    keep_timing_events(h, ev);
     if (pooled) pool_schedule(h, (hipStream_t)stream, T, batch_follows, true);
     pooled = h->pool && !h->pool_failed;
     done_steps += T;
@@ -1500,7 +1453,7 @@ int crafter_render(crafter_handle* h, const uint8_t* mask, uint8_t* out, void* s
   if (ready(h, "crafter_render")) return 1;
   if (!out) return fail(h, "crafter_render: null output");
   if (adopt_stream(h, (hipStream_t)stream)) return 1;
-  hipLaunchKernelGGL(crafter_render_kernel, dim3(h->cfg.num_envs), dim3(kStepThreads), h->lds_bytes,
+  hipLaunchKernelGGL(crafter_render_kernel, dim3(h->cfg.num_envs), dim3(kStepThreads), h->plan.render_lds,
                      (hipStream_t)stream, h->cfg, h->tb, h->st, mask, out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_render launch", e);
@@ -1516,7 +1469,7 @@ int crafter_symbolic(crafter_handle* h, const uint8_t* mask, uint8_t* local, flo
   if (lds > 64 * 1024) return fail(h, "crafter_symbolic: the local view is too large for the kernel's LDS strips");
   if (adopt_stream(h, (hipStream_t)stream)) return 1;
   const dim3 grid((unsigned)((h->cfg.num_envs + kSymbolicEnvs - 1) / kSymbolicEnvs)), block(kSymbolicThreads);
-  if (lds_layout(h->cfg).maps_in_lds)
+  if (h->plan.maps_in_lds)
     hipLaunchKernelGGL(crafter_symbolic_kernel<0>, grid, block, lds, (hipStream_t)stream, h->cfg, h->tb, h->st, mask, local, stats,
                        symbolic_strip_bytes(h->cfg));
   else

@@ -3,15 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <vector>
+
 #include "crafter_rollout.hpp"
 #include "dispatch_order.hpp"
 #include "wave_gfx950.hpp"
 
 namespace crafter {
 namespace {
-
-constexpr int kStepThreads = 256;      // = crafter_hip.hip (checked by the launchers' callers through cfg.step_threads)
-constexpr int kRequeueThreads = 256;
 
 // T steps of env blockIdx.x in one launch
 // (the default geometry's instances: six waves per SIMD -- 80 VGPRs -- are what their 26.9 KB of LDS allow per CU; left to
@@ -61,30 +60,20 @@ crafter_requeue_rollout_kernel(Config cfg, TablePtrs tb, StatePtrs st, const int
   }
 }
 
-#define CRAFTER_LAUNCH(kernel, grid, block, lds, stream, start, stop, ...)                                          \
-  do {                                                                                                              \
-    if ((start) != nullptr || (stop) != nullptr)                                                                    \
-      hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, start, stop, 0, __VA_ARGS__);                         \
-    else                                                                                                            \
-      hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                            \
-  } while (0)
-
 }  // namespace
 
 void launch_rollout(int instance, int num_envs, size_t lds, hipStream_t stream, hipEvent_t start, hipEvent_t stop, const Config& cfg,
                     const TablePtrs& tb, const StatePtrs& st, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
                     const StepCtl& ctl, const RolloutArgs& ra) {
   dim3 grid(num_envs + (ctl.order_build ? 1 : 0)), block(kStepThreads);
-  if (instance == 7)
-    CRAFTER_LAUNCH((crafter_rollout_kernel<1, 1, 1>), grid, block, lds, stream, start, stop, cfg, tb, st, actions, obs, reward, done, ctl, ra);
-  else if (instance == 6)
-    CRAFTER_LAUNCH((crafter_rollout_kernel<1, 1, 0>), grid, block, lds, stream, start, stop, cfg, tb, st, actions, obs, reward, done, ctl, ra);
-  else if (instance == 9)
-    CRAFTER_LAUNCH((crafter_rollout_kernel<0, 2, 1>), grid, block, lds, stream, start, stop, cfg, tb, st, actions, obs, reward, done, ctl, ra);
-  else if (instance == 4)
-    CRAFTER_LAUNCH((crafter_rollout_kernel<1, 0, 0>), grid, block, lds, stream, start, stop, cfg, tb, st, actions, obs, reward, done, ctl, ra);
-  else
-    CRAFTER_LAUNCH((crafter_rollout_kernel<0, 0, 0>), grid, block, lds, stream, start, stop, cfg, tb, st, actions, obs, reward, done, ctl, ra);
+  switch (instance) {
+#define CRAFTER_X(id, LM, GEO, RUL)                                                                                                                   \
+    case id:                                                                                                                                          \
+      CRAFTER_LAUNCH((crafter_rollout_kernel<LM, GEO, RUL>), grid, block, lds, stream, start, stop, cfg, tb, st, actions, obs, reward, done, ctl, ra); \
+      break;
+    CRAFTER_STEP_INSTANCES(CRAFTER_X)
+#undef CRAFTER_X
+  }
 }
 
 void launch_requeue_rollout(int grid, size_t lds, hipStream_t stream, hipEvent_t start, hipEvent_t stop, const Config& cfg,
@@ -95,8 +84,11 @@ void launch_requeue_rollout(int grid, size_t lds, hipStream_t stream, hipEvent_t
 }
 
 hipError_t rollout_allow_lds(int bytes) {
-  const void* big[] = {(const void*)crafter_rollout_kernel<0, 0, 0>, (const void*)crafter_rollout_kernel<0, 2, 1>, (const void*)crafter_rollout_kernel<1, 0, 0>,
-                       (const void*)crafter_requeue_rollout_kernel};
+  std::vector<const void*> big = {(const void*)crafter_requeue_rollout_kernel};
+#define CRAFTER_X(id, LM, GEO, RUL) \
+  if constexpr (GEO != 1) big.push_back((const void*)crafter_rollout_kernel<LM, GEO, RUL>);   // (the default geometry needs 25 KB)
+  CRAFTER_STEP_INSTANCES(CRAFTER_X)
+#undef CRAFTER_X
   for (const void* f : big) {
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return e;

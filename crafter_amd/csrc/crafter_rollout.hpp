@@ -7,8 +7,25 @@
 #include <hip/hip_runtime.h>
 
 #include "env_kernels.hpp"
+#include "launch_plan.hpp"
 
 namespace crafter {
+
+// Workgroup sizes both units launch with (compile-time: see WaveGfx950)
+constexpr int kStepThreads = 256;      // step / render / rollout workgroup
+constexpr int kRequeueThreads = 256;   // inline regeneration (rare): sized like a step workgroup, NOT like crafter_reset_kernel -- a
+                                       // 1024-thread workgroup needs a CU with all registers free, and with the world pool's kernels
+                                       // resident next to the step kernel even the EMPTY queue check would wait for one (measured: 32 us / step)
+
+// A launch with start / stop events attached (timing mode: hipExtLaunchKernelGGL) or a plain one -- the plain launch is
+// the cheaper call on the host, which is what bounds small batches (tools/host_overhead.py).
+#define CRAFTER_LAUNCH(kernel, grid, block, lds, stream, start, stop, ...)                                          \
+  do {                                                                                                              \
+    if ((start) != nullptr || (stop) != nullptr)                                                                    \
+      hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, start, stop, 0, __VA_ARGS__);                         \
+    else                                                                                                            \
+      hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                            \
+  } while (0)
 
 struct RolloutArgs {
   int T;
@@ -16,15 +33,14 @@ struct RolloutArgs {
   int32_t* stalled_at;    // [N] the step an env stopped at for want of a world (valid for the envs in the regeneration queue)
 };
 
-// instance: bit 2 = maps in LDS, bit 1 = default geometry, bit 0 = default rules (as crafter_step_instance reports it); 9 = maps and
-// slot table in global memory, default view and default rules compiled in (crafter_rollout_kernel<0, 2, 1>)
+// instance: LaunchPlan::instance (launch_plan.hpp CRAFTER_STEP_INSTANCES)
 void launch_rollout(int instance, int num_envs, size_t lds, hipStream_t stream, hipEvent_t start, hipEvent_t stop, const Config& cfg,
                     const TablePtrs& tb, const StatePtrs& st, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
                     const StepCtl& ctl, const RolloutArgs& ra);
 void launch_requeue_rollout(int grid, size_t lds, hipStream_t stream, hipEvent_t start, hipEvent_t stop, const Config& cfg,
                             const TablePtrs& tb, const StatePtrs& st, const int32_t* actions, uint8_t* obs, float* reward,
                             uint8_t* done, const StepCtl& ctl, const RolloutArgs& ra);
-// large worlds: lets the generic instances take `bytes` of dynamic LDS
+// large worlds (LaunchPlan::opt_in_lds): lets the generic instances take `bytes` of dynamic LDS
 hipError_t rollout_allow_lds(int bytes);
 
 }  // namespace crafter

@@ -7,6 +7,7 @@
 
 #include "wave_host.hpp"
 #include "../../crafter_amd/csrc/env_kernels.hpp"
+#include "../../crafter_amd/csrc/launch_plan.hpp"
 
 using namespace crafter;
 
@@ -22,7 +23,21 @@ void hostsim_struct_sizes(int32_t* out) {
 }
 
 int hostsim_lds_bytes(const Config* cfg) { return lds_layout(*cfg).total; }
-int hostsim_slot_map_derived(const Config* cfg) { return lds_layout(*cfg).maps_in_lds; }
+int hostsim_slot_map_derived(const Config* cfg) { return launch_plan(*cfg, false).maps_in_lds; }
+
+// The library's launch rule (launch_plan.hpp) and nothing else: the plan of a handle with this config and these rules, and the
+// choice one crafter_step call with these arguments makes.  order_env / split / wide / early: CRAFTER_ORDER, CRAFTER_SPLIT,
+// CRAFTER_STEP_WIDE, CRAFTER_STEP_EARLY as the library reads them (-1: unset).
+int hostsim_is_default_rules(const Rules* rules) { return is_default_rules(*rules); }
+void hostsim_launch_plan(const Config* cfg, int have_tables, int default_rules, int num_envs, int frames, int order_env, int split, int wide,
+                         int early, int lds_pad, int rollout_lds_pad, int32_t out[12]) {
+  const LaunchPlan p = launch_plan(*cfg, have_tables && default_rules, lds_pad, rollout_lds_pad);
+  const bool ordered = keeps_dispatch_order(num_envs, order_env);
+  const StepKernel k = choose_step(p, num_envs, frames != 0, ordered, split, wide, early);
+  const int32_t v[12] = {p.instance, p.maps_in_lds, p.gen_geo, p.step_lds, p.rollout_lds, p.render_lds, p.reset_lds, p.night_px, p.opt_in_lds,
+                         (int32_t)k, ordered && !is_split(k), step_early_frame(num_envs, early)};
+  memcpy(out, v, sizeof(v));
+}
 // LDS per workgroup of the step kernel's default instance, and of the two kernels of the split step
 int hostsim_step_lds_bytes(const Config* cfg) { return lds_layout(*cfg, 1).total; }
 int hostsim_rules_lds_bytes(const Config* cfg) { return lane_layout(*cfg).total; }
@@ -101,9 +116,9 @@ void hostsim_set_noise_ahead(int on) { g_noise_ahead = on; }
 int hostsim_step(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const int32_t* actions,
                  uint8_t* obs, float* reward, uint8_t* done, int pool_mode) {
   std::vector<uint8_t> lds(lds_layout(*cfg).total + frame_layout(*cfg).total + 64);
-  // (the library splits the default instance only: default geometry AND the compiled-in rules)
-  bool split = g_split && is_default_geometry(*cfg) && lds_layout(*cfg).maps_in_lds && lane_layout_ok(*cfg) &&
-               memcmp(tb->rules, &kDefaultRules, sizeof(Rules)) == 0;
+  const LaunchPlan plan = launch_plan(*cfg, is_default_rules(*tb->rules));
+  // (the library splits the default instance only: choose_step; no dispatch order here, and always the early frame -- see below)
+  bool split = lane_layout_ok(*cfg) && is_split(choose_step(plan, cfg->num_envs, cfg->render_obs && obs, false, g_split ? 1 : 0, 0, 1));
   StepCtl ctl;
   ctl.parity = 0;
   ctl.gen_parity = pool_mode ? 0 : -1;
@@ -119,19 +134,25 @@ int hostsim_step(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, co
   for (int env = 0; env < cfg->num_envs; env++) {
     memset(lds.data(), 0xCD, lds.size());
     WaveHost w;
+    StepCtl big = ctl;   // big_layout: census in place, night pixels in global scratch
+    big.night_px = night_px.data();
     if (split) {
       step_body<WaveHost, -1, 1, LaneSlots, 1>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
-    } else if (is_default_geometry(*cfg))   // as crafter_step_kernel does: one-byte slot ids for crafter.Env()'s defaults
-      step_body<WaveHost, -1, 0, uint8_t>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
-    else if (!lds_layout(*cfg).maps_in_lds) {   // crafter_step_kernel<0, 0, 0>: big_layout -- census in place, night pixels in global scratch
-      StepCtl big = ctl;
-      big.night_px = night_px.data();
-      if (is_default_view(*cfg) && memcmp(tb->rules, &kDefaultRules, sizeof(Rules)) == 0)   // crafter_step_kernel<0, 2, 1>: the default rules compiled in
+    } else switch (plan.instance) {   // crafter_step_kernel<LM, GEO, RUL>; here LM -1 for maps in "LDS", and the staged rules where they are
+      case kInstance111:
+      case kInstance110:   // one-byte slot ids for crafter.Env()'s defaults
+        step_body<WaveHost, -1, 0, uint8_t>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
+        break;
+      case kInstance100:
+        step_body<WaveHost, -1, 0, uint16_t>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
+        break;
+      case kInstance021:   // the default rules compiled in
         step_body<WaveHost, 0, 1, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, big);
-      else
+        break;
+      case kInstance000:
         step_body<WaveHost, 0, 0, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, big);
-    } else
-      step_body<WaveHost, -1, 0, uint16_t>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
+        break;
+    }
   }
   if (frames) {   // the frame kernel
     for (int env = 0; env < cfg->num_envs; env++) {
@@ -161,6 +182,8 @@ int hostsim_step_n(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, 
                    uint8_t* obs, float* reward, uint8_t* done, int pool_mode, int stretch) {
   std::vector<uint8_t> lds(lds_layout(*cfg).total + 64);
   std::vector<int32_t> stalled_at((size_t)cfg->num_envs, -1);
+  const LaunchPlan plan = launch_plan(*cfg, is_default_rules(*tb->rules));
+  std::vector<uint32_t> night_px(plan.night_px ? (size_t)cfg->num_envs * frame_night_px_words(*cfg) : 0);   // (big_layout)
   StepCtl ctl;
   ctl.parity = 0;
   ctl.gen_parity = pool_mode ? 0 : -1;
@@ -175,19 +198,23 @@ int hostsim_step_n(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, 
     for (int env = 0; env < cfg->num_envs; env++) {
       memset(lds.data(), 0xCD, lds.size());
       WaveHost w;
-      if (is_default_geometry(*cfg))
-        rollout_body<WaveHost, -1, 0, uint8_t>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
-      else if (!lds_layout(*cfg).maps_in_lds) {   // crafter_rollout_kernel<0, 0, 0>: big_layout, the slot table in global memory
-        static std::vector<uint32_t> night_px;
-        night_px.resize((size_t)cfg->num_envs * frame_night_px_words(*cfg));
-        StepCtl big = ctl;
-        big.night_px = night_px.data();
-        if (is_default_view(*cfg) && memcmp(tb->rules, &kDefaultRules, sizeof(Rules)) == 0)   // crafter_rollout_kernel<0, 2, 1>
+      StepCtl big = ctl;
+      big.night_px = night_px.data();
+      switch (plan.instance) {   // crafter_rollout_kernel<LM, GEO, RUL>, the template arguments as in hostsim_step
+        case kInstance111:
+        case kInstance110:
+          rollout_body<WaveHost, -1, 0, uint8_t>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
+          break;
+        case kInstance100:
+          rollout_body<WaveHost, -1, 0, uint16_t>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
+          break;
+        case kInstance021:
           rollout_body<WaveHost, 0, 1, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, big, T, obs_stride, stalled_at.data());
-        else
+          break;
+        case kInstance000:
           rollout_body<WaveHost, 0, 0, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, big, T, obs_stride, stalled_at.data());
-      } else
-        rollout_body<WaveHost, -1, 0, uint16_t>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
+          break;
+      }
     }
     if (cfg->auto_reset) {
       int32_t* q = st->reset_q;

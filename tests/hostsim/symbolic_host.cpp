@@ -4,19 +4,19 @@
 #include <vector>
 
 #include "wave_host.hpp"
-#include "../../crafter_amd/csrc/env_kernels.hpp"   // lds_layout: the chooser between the two object paths, as the library's
+#include "../../crafter_amd/csrc/launch_plan.hpp"   // LaunchPlan::maps_in_lds: the chooser between the two object paths, as the library's
 #include "../../crafter_amd/csrc/symbolic.hpp"
 
 using namespace crafter;
 
 extern "C" {
 
-int hostsim_symbolic_map_is_state(const Config* cfg) { return lds_layout(*cfg).maps_in_lds ? 0 : 1; }
+int hostsim_symbolic_map_is_state(const Config* cfg) { return launch_plan(*cfg, false).maps_in_lds ? 0 : 1; }
 
 // cfg / tb / st: a HostSimEnv's.  local: [N][2][gw][gh] bytes or null, stats: [N][n_items + 4] floats or null.
 int hostsim_symbolic(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const uint8_t* mask, uint8_t* local, float* stats) {
   std::vector<uint32_t> strip(symbolic_strip_bytes(*cfg) / 4);
-  const bool map_is_state = !lds_layout(*cfg).maps_in_lds;
+  const bool map_is_state = !launch_plan(*cfg, false).maps_in_lds;
   // one env beyond the batch, as the last workgroup's spare waves: must return without touching anything
   for (int env = 0; env < cfg->num_envs + 1; env++) {
     memset(strip.data(), 0xCD, strip.size() * 4);   // poisoned "LDS"
