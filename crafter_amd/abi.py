@@ -1,7 +1,9 @@
-"""ctypes / numpy mirrors of the plain-data structs in crafter_amd/csrc/types.hpp.
+"""ctypes / numpy mirrors of the plain-data structs, constants and enums in include/crafter_hip_types.h (TablePtrs: the
+library's own, crafter_amd/csrc/types.hpp).
 
 The C-ABI library (include/crafter_hip.h) exchanges these by pointer.  ``check_sizes`` compares
-every sizeof with what the loaded library reports, so a layout drift fails loudly at import.
+every sizeof with what the loaded library reports, so a layout drift fails loudly at import;
+tests/test_host_logic.py compares every field offset, size and value with the header.
 """
 import ctypes as C
 
@@ -30,7 +32,7 @@ STATUS_NAMES = {
     ST_BAD_COPY: 'ST_BAD_COPY: copy_envs / load_state refused its indices (out of range, duplicate or overlapping destination); nothing was copied',
 }
 
-# texture slots of TablePtrs.tex_tile (types.hpp TEX_*)
+# texture slots of TablePtrs.tex_tile (crafter_hip_types.h CRAFTER_TEX_*)
 TEX_MATERIAL0 = 0
 (TEX_PLAYER_LEFT, TEX_PLAYER_RIGHT, TEX_PLAYER_UP, TEX_PLAYER_DOWN, TEX_PLAYER_SLEEP, TEX_COW,
  TEX_ZOMBIE, TEX_SKELETON, TEX_ARROW_LEFT, TEX_ARROW_RIGHT, TEX_ARROW_UP, TEX_ARROW_DOWN, TEX_PLANT,

@@ -2,7 +2,7 @@
 
 This is the batched form of the reference's ``crafter.Env`` (env.py:25-133): same constructor
 arguments per environment, ``reset()`` / ``step(actions)`` / ``render()`` over tensors.  All world
-state lives in caller-owned torch tensors on the GPU (struct-of-arrays, types.hpp StatePtrs); this
+state lives in caller-owned torch tensors on the GPU (struct-of-arrays, crafter_hip_types.h crafter_state_ptrs); this
 class only allocates them, uploads the host-evaluated tables and enqueues kernels on the current
 torch stream.  There is no CPU implementation behind it.
 """
@@ -402,7 +402,7 @@ class BatchedEnv:
     return out
 
   # ------------------------------------------------------------------ symbolic observation (include/crafter_hip.h crafter_symbolic)
-  _OBJECT_CLASSES = ('player', 'cow', 'zombie', 'skeleton', 'arrow', 'plant')   # env.py:47-49, types.hpp T_*
+  _OBJECT_CLASSES = ('player', 'cow', 'zombie', 'skeleton', 'arrow', 'plant')   # env.py:47-49, crafter_hip_types.h CRAFTER_T_*
 
   @property
   def symbolic_shape(self):

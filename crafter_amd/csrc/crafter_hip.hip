@@ -15,7 +15,6 @@
 #include <string>
 #include <vector>
 
-#define CRAFTER_HIP_INTERNAL
 #include "../../include/crafter_hip.h"
 #include "crafter_rollout.hpp"
 #include "dispatch_order.hpp"
@@ -26,77 +25,6 @@
 #include "wave_gfx950.hpp"
 
 using namespace crafter;
-
-// crafter_config / crafter_rules / crafter_state_ptrs are the C names of these structs
-struct crafter_config : Config {};
-struct crafter_rules : Rules {};
-struct crafter_state_ptrs : StatePtrs {};
-
-// The C99 layouts a binding compiles against (include/crafter_hip_types.h), checked field by field against the kernels'
-// own definitions (types.hpp): a drift is a build error, not a silent misread.
-namespace cabi {
-#include "../../include/crafter_hip_types.h"
-}
-#define CRAFTER_SAME_FIELD(CT, T, f) \
-  static_assert(offsetof(cabi::CT, f) == offsetof(T, f) && sizeof(((cabi::CT*)0)->f) == sizeof(((T*)0)->f), #CT "." #f)
-#define CRAFTER_SAME_SIZE(CT, T) static_assert(sizeof(cabi::CT) == sizeof(T) && alignof(cabi::CT) == alignof(T), #CT)
-CRAFTER_SAME_SIZE(crafter_obj, Obj);
-CRAFTER_SAME_FIELD(crafter_obj, Obj, type); CRAFTER_SAME_FIELD(crafter_obj, Obj, health); CRAFTER_SAME_FIELD(crafter_obj, Obj, fx);
-CRAFTER_SAME_FIELD(crafter_obj, Obj, fy); CRAFTER_SAME_FIELD(crafter_obj, Obj, x); CRAFTER_SAME_FIELD(crafter_obj, Obj, y);
-CRAFTER_SAME_FIELD(crafter_obj, Obj, aux); CRAFTER_SAME_FIELD(crafter_obj, Obj, pad);
-CRAFTER_SAME_SIZE(crafter_item_list, ItemList);
-CRAFTER_SAME_FIELD(crafter_item_list, ItemList, n); CRAFTER_SAME_FIELD(crafter_item_list, ItemList, item);
-CRAFTER_SAME_FIELD(crafter_item_list, ItemList, amount); CRAFTER_SAME_FIELD(crafter_item_list, ItemList, ach);
-CRAFTER_SAME_SIZE(crafter_collect_rule, CollectRule);
-CRAFTER_SAME_FIELD(crafter_collect_rule, CollectRule, valid); CRAFTER_SAME_FIELD(crafter_collect_rule, CollectRule, leaves);
-CRAFTER_SAME_FIELD(crafter_collect_rule, CollectRule, probability); CRAFTER_SAME_FIELD(crafter_collect_rule, CollectRule, require);
-CRAFTER_SAME_FIELD(crafter_collect_rule, CollectRule, receive);
-CRAFTER_SAME_SIZE(crafter_place_rule, PlaceRule);
-CRAFTER_SAME_FIELD(crafter_place_rule, PlaceRule, valid); CRAFTER_SAME_FIELD(crafter_place_rule, PlaceRule, is_object);
-CRAFTER_SAME_FIELD(crafter_place_rule, PlaceRule, material); CRAFTER_SAME_FIELD(crafter_place_rule, PlaceRule, ach);
-CRAFTER_SAME_FIELD(crafter_place_rule, PlaceRule, where_mask); CRAFTER_SAME_FIELD(crafter_place_rule, PlaceRule, uses);
-CRAFTER_SAME_SIZE(crafter_make_rule, MakeRule);
-CRAFTER_SAME_FIELD(crafter_make_rule, MakeRule, valid); CRAFTER_SAME_FIELD(crafter_make_rule, MakeRule, item);
-CRAFTER_SAME_FIELD(crafter_make_rule, MakeRule, gives); CRAFTER_SAME_FIELD(crafter_make_rule, MakeRule, ach);
-CRAFTER_SAME_FIELD(crafter_make_rule, MakeRule, nearby_mask); CRAFTER_SAME_FIELD(crafter_make_rule, MakeRule, uses);
-CRAFTER_SAME_SIZE(crafter_rules, Rules);
-#define R_(f) CRAFTER_SAME_FIELD(crafter_rules, Rules, f)
-R_(n_actions); R_(n_materials); R_(n_items); R_(n_achievements); R_(action_kind); R_(action_arg); R_(item_max); R_(item_init);
-R_(walkable_mask); R_(player_walkable_mask); R_(arrow_walkable_mask); R_(arrow_breaks_mask);
-R_(mat_water); R_(mat_grass); R_(mat_stone); R_(mat_path); R_(mat_sand); R_(mat_tree); R_(mat_lava); R_(mat_coal); R_(mat_iron);
-R_(mat_diamond); R_(mat_table); R_(mat_furnace); R_(item_health); R_(item_food); R_(item_drink); R_(item_energy);
-R_(item_wood_sword); R_(item_stone_sword); R_(item_iron_sword); R_(ach_wake_up); R_(ach_eat_plant); R_(ach_defeat_zombie);
-R_(ach_defeat_skeleton); R_(ach_eat_cow); R_(collect); R_(place); R_(make);
-#undef R_
-CRAFTER_SAME_SIZE(crafter_config, Config);
-#define C_(f) CRAFTER_SAME_FIELD(crafter_config, Config, f)
-C_(num_envs); C_(W); C_(H); C_(view_w); C_(view_h); C_(size_w); C_(size_h); C_(unit_x); C_(unit_y); C_(local_gw); C_(local_gh);
-C_(item_gw); C_(item_gh); C_(border_x); C_(border_y); C_(icon_w); C_(icon_h); C_(digit_w); C_(digit_h); C_(max_objects);
-C_(nchunk_x); C_(nchunk_y); C_(length); C_(update_dist); C_(n_daylight); C_(auto_reset); C_(want_semantic); C_(render_obs);
-C_(reward); C_(step_threads); C_(reset_threads); C_(gen_period);
-#undef C_
-CRAFTER_SAME_SIZE(crafter_env_rec, EnvRec);
-#define E_(f) CRAFTER_SAME_FIELD(crafter_env_rec, EnvRec, f)
-E_(mt_pos); E_(step); E_(episode); E_(nobj); E_(seed_lane); E_(nchunks_seen); E_(status); E_(inv); E_(ach); E_(hunger2);
-E_(thirst2); E_(fatigue2); E_(recover2); E_(player_last_health); E_(env_last_health); E_(unlocked); E_(sleeping); E_(dhealth);
-E_(new_unlocked); E_(dead); E_(done); E_(needs_reset); E_(ep_dhealth); E_(ep_unlock_steps); E_(pad);
-#undef E_
-CRAFTER_SAME_SIZE(crafter_pool_hdr, PoolHdr);
-CRAFTER_SAME_FIELD(crafter_pool_hdr, PoolHdr, ready); CRAFTER_SAME_FIELD(crafter_pool_hdr, PoolHdr, mt_pos);
-CRAFTER_SAME_FIELD(crafter_pool_hdr, PoolHdr, nobj); CRAFTER_SAME_FIELD(crafter_pool_hdr, PoolHdr, nchunks_seen);
-CRAFTER_SAME_FIELD(crafter_pool_hdr, PoolHdr, pad); CRAFTER_SAME_FIELD(crafter_pool_hdr, PoolHdr, pending); CRAFTER_SAME_FIELD(crafter_pool_hdr, PoolHdr, pad2);
-CRAFTER_SAME_SIZE(crafter_state_ptrs, StatePtrs);
-#define S_(f) CRAFTER_SAME_FIELD(crafter_state_ptrs, StatePtrs, f)
-S_(mat); S_(objmap); S_(objs); S_(mt); S_(rec); S_(chunk_order); S_(chunk_seen); S_(census); S_(semantic); S_(prof); S_(reset_q);
-S_(pool_mat); S_(pool_objs); S_(pool_mt); S_(pool_hdr); S_(pool_chunk_order); S_(gen_q); S_(gen_latest); S_(terminal);
-S_(pool_stats); S_(pool_perm); S_(pool_census);
-#undef S_
-static_assert(cabi::CRAFTER_TEX_COUNT == TEX_COUNT && cabi::CRAFTER_TEX_PLANT_RIPE == TEX_PLANT_RIPE && CRAFTER_MT_N == MT_N &&
-                  CRAFTER_MAX_ITEMS == MAX_ITEMS && CRAFTER_MAX_ACH == MAX_ACH && CRAFTER_MAX_MATERIALS == MAX_MATERIALS &&
-                  CRAFTER_MAX_ACTIONS == MAX_ACTIONS && CRAFTER_MAX_PLACE == MAX_PLACE && CRAFTER_MAX_MAKE == MAX_MAKE &&
-                  CRAFTER_MAX_USES == MAX_USES && CRAFTER_CHUNK == CHUNK,
-              "constants of crafter_hip_types.h");
-static_assert(cabi::CRAFTER_ST_BAD_COPY == ST_BAD_COPY && cabi::CRAFTER_ST_POOL_MISMATCH == ST_POOL_MISMATCH, "status bits of crafter_hip_types.h");
 
 namespace {
 
@@ -791,7 +719,7 @@ int crafter_upload_tables(crafter_handle* h, const crafter_host_tables* t) {
   const Config& c = h->cfg;
   if (t->n_tex_tile != TEX_COUNT || t->n_tex_icon != MAX_ITEMS || t->n_tex_digit != 11 ||
       t->n_tex_alpha != TEX_COUNT + MAX_ITEMS + 11 || t->n_item_pos != MAX_ITEMS * 4 || t->n_unit255 != 256)
-    return fail(h, "crafter_upload_tables: table sizes do not match types.hpp");
+    return fail(h, "crafter_upload_tables: table sizes do not match crafter_hip_types.h");
   if (t->n_daylight != c.n_daylight) return fail(h, "crafter_upload_tables: daylight table size != cfg.n_daylight");
   if (t->n_daylight >= (1 << 24)) return fail(h, "crafter_upload_tables: more than 2^24 - 1 steps per episode");   // (the step kernels keep the step counter in 24 bits of an LDS word)
   if (t->n_vignette != c.local_gw * c.unit_x * c.local_gh * c.unit_y)

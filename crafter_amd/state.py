@@ -1,4 +1,4 @@
-"""Shapes and views of the per-env state buffers (types.hpp StatePtrs), backend-agnostic.
+"""Shapes and views of the per-env state buffers (crafter_hip_types.h crafter_state_ptrs), backend-agnostic.
 
 The buffers themselves are allocated by the caller (torch tensors on the GPU in the product);
 this module only says how big they are and how to read them back as structured numpy arrays.

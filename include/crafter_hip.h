@@ -20,9 +20,10 @@
  *
  * Struct layouts (crafter_config, crafter_rules, crafter_state_ptrs, crafter_obj, crafter_env_rec) are plain C99
  * in crafter_hip_types.h, included below: this header is self-contained for a C / Rust / Go / Java binding
- * (tests/c/boundary_test.c drives the whole path from C with nothing else).  The kernels' own C++ definitions
- * (crafter_amd/csrc/types.hpp) are static_asserted field by field against that file when the library is built;
- * crafter_amd/abi.py is the ctypes mirror, and crafter_struct_sizes lets any binding verify its own.
+ * (tests/c/boundary_test.c drives the whole path from C with nothing else).  That file is the only statement of the
+ * layouts: the library's kernels are compiled against it (crafter_amd/csrc/types.hpp merely aliases its structs).
+ * crafter_amd/abi.py is the ctypes mirror, checked against it offset by offset in the test suite, and
+ * crafter_struct_sizes lets any binding verify its own.
  */
 #ifndef CRAFTER_HIP_H_
 #define CRAFTER_HIP_H_
@@ -35,13 +36,7 @@ extern "C" {
 #endif
 
 typedef struct crafter_handle crafter_handle;
-#ifdef CRAFTER_HIP_INTERNAL   /* the library itself: the C names are its own C++ structs (checked against the C layouts) */
-typedef struct crafter_config crafter_config;          /* crafter::Config    */
-typedef struct crafter_rules crafter_rules;            /* crafter::Rules     */
-typedef struct crafter_state_ptrs crafter_state_ptrs;  /* crafter::StatePtrs */
-#else
 #include "crafter_hip_types.h"
-#endif
 
 /* Host-side tables handed to crafter_upload_tables (all HOST pointers, copied by the library).
  * They carry everything the reference evaluates with numpy / Pillow / its yaml at run time:
@@ -50,7 +45,7 @@ typedef struct crafter_state_ptrs crafter_state_ptrs;  /* crafter::StatePtrs */
 typedef struct crafter_host_tables {
   const crafter_rules* rules;
   const uint8_t* atlas;      size_t atlas_bytes;   /* RGBA texels, [x][y] per texture          */
-  const int32_t* tex_tile;   int32_t n_tex_tile;   /* byte offsets, types.hpp TEX_* slots      */
+  const int32_t* tex_tile;   int32_t n_tex_tile;   /* byte offsets, CRAFTER_TEX_* slots         */
   const int32_t* tex_icon;   int32_t n_tex_icon;   /* per item                                 */
   const int32_t* tex_digit;  int32_t n_tex_digit;  /* '1'..'9' at [1..9], 'unknown' at [10]    */
   const uint8_t* tex_alpha;  int32_t n_tex_alpha;  /* 1 = source PNG had an alpha channel      */

@@ -4,7 +4,8 @@ import subprocess
 
 HERE = pathlib.Path(__file__).resolve().parent
 OUT = HERE / '_build' / 'libhostsim.so'
-SRCS = [HERE / 'hostsim.cpp', HERE / 'wave_host.hpp'] + sorted((HERE.parent.parent / 'crafter_amd' / 'csrc').glob('*.hpp'))
+SRCS = [HERE / 'hostsim.cpp', HERE / 'wave_host.hpp'] + sorted((HERE.parent.parent / 'crafter_amd' / 'csrc').glob('*.hpp')) + [
+    HERE.parent.parent / 'include' / 'crafter_hip_types.h']   # csrc/types.hpp includes it
 
 
 def build(force=False, defines=(), tag=''):

@@ -8,7 +8,8 @@ import numpy as np
 
 HERE = pathlib.Path(__file__).resolve().parent
 OUT = HERE / '_build' / 'libhostsim_symbolic.so'
-SRCS = [HERE / 'symbolic_host.cpp', HERE / 'wave_host.hpp'] + sorted((HERE.parent.parent / 'crafter_amd' / 'csrc').glob('*.hpp'))
+SRCS = [HERE / 'symbolic_host.cpp', HERE / 'wave_host.hpp'] + sorted((HERE.parent.parent / 'crafter_amd' / 'csrc').glob('*.hpp')) + [
+    HERE.parent.parent / 'include' / 'crafter_hip_types.h']   # csrc/types.hpp includes it
 
 _lib = None
 

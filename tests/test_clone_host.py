@@ -70,12 +70,15 @@ def test_new_entry_points_declared_listed_and_exported():
 
 
 def test_bad_copy_status_bit_consistent():
+  """The seven status bits of abi.py are distinct, each has its text, and each is the C header's value of that name."""
   from crafter_amd import abi
+  from tests import abi_layout
   assert abi.ST_BAD_COPY == 64 and 'ST_BAD_COPY' in abi.STATUS_NAMES[abi.ST_BAD_COPY]
-  types_hpp = (ROOT / 'crafter_amd' / 'csrc' / 'types.hpp').read_text()
-  types_h = (ROOT / 'include' / 'crafter_hip_types.h').read_text()
-  assert int(re.search(r'\bST_BAD_COPY = (\d+)u', types_hpp).group(1)) == abi.ST_BAD_COPY
-  assert int(re.search(r'\bCRAFTER_ST_BAD_COPY = (\d+)', types_h).group(1)) == abi.ST_BAD_COPY
+  bits = {name: value for name, value in abi_layout.python_values().items() if name.startswith('ST_')}
+  assert len(bits) == 7 and len(set(bits.values())) == 7 and set(bits.values()) == set(abi.STATUS_NAMES)
+  header = abi_layout.header_report()[2]
+  assert header['ST_BAD_COPY'] == abi.ST_BAD_COPY
+  assert {name: header[name] for name in bits} == bits
   assert len({abi.ST_OBJ_OVERFLOW, abi.ST_BAD_ACTION, abi.ST_STEP_OVERFLOW, abi.ST_CHUNK_OVERFLOW, abi.ST_POOL_MISMATCH,
               abi.ST_PIPE_STALL, abi.ST_BAD_COPY}) == 7
 

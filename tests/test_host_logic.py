@@ -253,6 +253,28 @@ def test_c_header_is_self_contained_c99(tmp_path):
   assert cfg.n_daylight == 10002 and (tmp_path / 'tables.bin').stat().st_size > 100000
 
 
+def test_python_mirror_matches_the_c_header():
+  """crafter_amd/abi.py (and lib.HostTablesC) against include/crafter_hip_types.h as a C compiler reads it: sizeof of every
+  struct, offset and size of every field, the number of fields (tests/abi_layout.py: a field missing on either side does not
+  compile) and every constant and enum value, under the names both sides give them."""
+  import shutil
+  import pytest
+  from tests import abi_layout
+  if not shutil.which('gcc'):
+    pytest.skip('needs gcc')
+  sizes, fields, values = abi_layout.header_report()
+  layouts = abi_layout.python_layouts()
+  assert set(sizes) == set(layouts) and len(fields) == sum(len(f) for _, f in layouts.values())
+  for struct, (size, flds) in layouts.items():
+    assert sizes[struct] == size, (struct, sizes[struct], size)
+    for name, offset, fsize, _ in flds:
+      assert fields[struct, name] == (offset, fsize), (struct, name, fields[struct, name], (offset, fsize))
+  mine = abi_layout.python_values()
+  assert set(mine) == abi_layout.header_value_names(), set(mine) ^ abi_layout.header_value_names()
+  assert mine == values, {n: (mine[n], values[n]) for n in mine if mine[n] != values[n]}
+  assert len(mine) == 7 + 6 + 7 + 16 + 7 + 2   # T_*, A_*, ST_*, TEX_*, MAX_*, MT_N and CHUNK
+
+
 def test_daylight_table_grows_ahead_of_the_longest_episode():
   """BatchedEnv._grow_daylight (Env(length=None), env.py:29): the host-side policy alone, on a stand-in for the device --
   the bound kept between calls is conservative, the step counters are read back only when it nears the end of the table,
