@@ -313,19 +313,27 @@ class BatchedEnv:
     self._keep = mask
     return self.obs
 
-  def step(self, actions, info=True, out=None):
+  def step(self, actions, info=True, out=None, final=False):
     """Env.step() (env.py:83-118) for all envs.  actions: int tensor [N] on the device.
     Returns (obs u8[N,H,W,3], reward f32[N], done u8[N], info dict of device tensor views).
     With auto_reset, a finished env comes back already regenerated (its obs is the first frame
     of the next episode; done/reward still describe the finished step).
     out = (obs or None, reward, done): device tensors the kernels write instead of self.obs / self.reward /
-    self.done (e.g. the send buffer of crafter_amd.dist.StepExchange); obs must be 16-byte aligned."""
+    self.done (e.g. the send buffer of crafter_amd.dist.StepExchange); obs must be 16-byte aligned.
+    final=True (auto_reset batches only; crafter_step_final): the info dict also carries, whatever `info` is, what the
+    finished episodes left behind -- 'final_obs' u8[N,H,W,3], the frame the reference returns with done=True (absent with
+    render=False); 'terminated' u8[N], 1 if the player died (discount == 0), 0 if the episode only ran into `length`;
+    'final_local' / 'final_stats', symbolic()'s pair of the terminal state.  These are persistent device tensors of the batch,
+    zero-initialised at first use; a step only writes the rows of envs it finished: rows are valid where done != 0.  Everything
+    else the call returns and leaves behind is bit-identical to final=False, and the two may be mixed."""
     actions = self._actions(actions)
     obs, reward, done = self.obs, self.reward, self.done
     if out is not None:
       obs = obs if out[0] is None else out[0]
       reward, done = out[1], out[2]
       self._check_out(obs, self.obs), self._check_out(reward, self.reward), self._check_out(done, self.done)
+    if final:
+      return self._step_final(actions, obs, reward, done, info)
     if self._unbounded:
       self._grow_daylight(1)
     with torch.cuda.device(self.device):
@@ -334,6 +342,39 @@ class BatchedEnv:
           C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), self._stream()))
     self._keep = (actions, obs, reward, done)
     return obs, reward, done, (self.info() if info else {})
+
+  def final_buffers(self):
+    """The persistent device tensors step(final=True) writes and returns in its info dict: {'final_obs' (absent with
+    render=False), 'terminated', 'final_local', 'final_stats'}; allocated at first use, zero-initialised."""
+    if getattr(self, '_final', None) is None:
+      ls, ss = self.symbolic_shape
+      n = self.num_envs
+      with torch.cuda.device(self.device):
+        f = {'terminated': torch.zeros(n, dtype=torch.uint8, device=self.device),
+             'final_local': torch.zeros((n,) + ls, dtype=torch.uint8, device=self.device),
+             'final_stats': torch.zeros((n,) + ss, dtype=torch.float32, device=self.device)}
+        if self.cfg.render_obs:
+          f['final_obs'] = torch.zeros_like(self.obs)
+      self._final = f
+    return self._final
+
+  def _step_final(self, actions, obs, reward, done, info):
+    if not self.cfg.auto_reset:
+      raise ValueError('step(final=True) needs auto_reset=True: without it obs already is the finished episode\'s last frame')
+    if not hasattr(self._lib, 'crafter_step_final'):
+      raise _libmod.CrafterLibError('the loaded library has no crafter_step_final (an older build): step(final=True) is not available')
+    f = self.final_buffers()
+    if self._unbounded:
+      self._grow_daylight(1)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(self.device):
+      self._check(self._lib.crafter_step_final(
+          self._handle, ptr(actions), ptr(obs), ptr(reward), ptr(done), ptr(f['final_obs']) if 'final_obs' in f else None,
+          ptr(f['terminated']), ptr(f['final_local']), ptr(f['final_stats']), self._stream()))
+    self._keep = (actions, obs, reward, done)
+    out = self.info() if info else {}
+    out.update(f)
+    return obs, reward, done, out
 
   def rollout(self, actions, out=None, obs=True):
     """T steps in one call for policies that choose their actions without looking at the observations (random,

@@ -166,6 +166,25 @@ crafter_requeue_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity,
   }
 }
 
+// crafter_step_final: takes the place of crafter_requeue_reset_kernel behind a step launch that ran with StepCtl::gen_parity = -1,
+// so that EVERY env that finished is in the queue with its terminal state complete in global memory and no frame drawn.  Per
+// env: terminated, the terminal state's symbolic pair and frame, then Env.reset from the pool or inline (final_reset_body).
+__global__ void __launch_bounds__(kRequeueThreads, 2)
+crafter_requeue_final_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity, int gen_parity, uint32_t safe_seq,
+                             uint8_t* __restrict__ obs, int32_t* __restrict__ next_step, FinalOut fo) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int32_t* q = st.reset_q + (size_t)parity * (cfg.num_envs + 4);
+  int count = q[0];
+  if (count > cfg.num_envs) count = cfg.num_envs;
+  if (blockIdx.x == 0 && threadIdx.x == 0) st.reset_q[(size_t)(1 - parity) * (cfg.num_envs + 4)] = 0;
+  for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
+    WaveGfx950<kRequeueThreads> w;
+    int env = q[4 + k];
+    if (env >= 0 && env < cfg.num_envs) final_reset_body(w, smem, env, cfg, tb, st, obs, gen_parity, safe_seq, next_step, fo);
+    __syncthreads();
+  }
+}
+
 // Env.reset.  With the world pool on (gen_parity >= 0) the workgroup goes on to generate the NEXT episode's world into
 // the env's pool entry, stamped with batch sequence 1 (trusted from the start: this kernel precedes every later step in
 // stream order) -- that world may be needed a few dozen steps from now, earlier than any batch could deliver it.
@@ -608,7 +627,8 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
     CRAFTER_STEP_INSTANCES(CRAFTER_X)
 #undef CRAFTER_X
     for (const void* f : {(const void*)crafter_reset_kernel, (const void*)crafter_gen_resolve_kernel<0>,
-                          (const void*)crafter_requeue_reset_kernel, (const void*)crafter_render_kernel})
+                          (const void*)crafter_requeue_reset_kernel, (const void*)crafter_requeue_final_kernel,
+                          (const void*)crafter_render_kernel})
       big.push_back(f);
     hipError_t er = rollout_allow_lds(h->plan.render_lds);   // the rollout kernels live in crafter_rollout.hip
     if (er != hipSuccess) {
@@ -1099,7 +1119,18 @@ static int requeue_grid(const crafter_handle* h, const StepCtl& ctl) {
   int full = h->cfg.num_envs < kRequeueGrid ? h->cfg.num_envs : kRequeueGrid;
   return (ctl.gen_parity >= 0 && full > h->requeue_grid) ? h->requeue_grid : full;
 }
-static void launch_requeue(crafter_handle* h, const StepCtl& ctl, uint8_t* obs, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+// fin: crafter_step_final -- the step kernels ran with gen_parity = -1 and queued every finished env; the kernel that walks the
+// queue draws the terminal frame first and takes worlds from the pool itself (pool_parity: the segment collecting requests,
+// -1: pool off).  All of them come through here: the full grid, whatever the pool does.
+static void launch_requeue(crafter_handle* h, const StepCtl& ctl, uint8_t* obs, hipStream_t stream, hipEvent_t start, hipEvent_t stop,
+                           const FinalOut* fin = nullptr, int pool_parity = -1) {
+  if (fin) {
+    const int grid = h->cfg.num_envs < kRequeueGrid ? h->cfg.num_envs : kRequeueGrid;
+    const int lds = h->plan.render_lds > h->plan.reset_lds ? h->plan.render_lds : h->plan.reset_lds;
+    CRAFTER_LAUNCH(crafter_requeue_final_kernel, dim3(grid), dim3(kRequeueThreads), lds, stream, start, stop, h->cfg, h->tb, h->st, ctl.parity,
+                   pool_parity, ctl.safe_seq, obs, ctl.next_step, *fin);
+    return;
+  }
   CRAFTER_LAUNCH(crafter_requeue_reset_kernel, dim3(requeue_grid(h, ctl)), dim3(kRequeueThreads), h->plan.reset_lds, stream, start, stop,
                         h->cfg, h->tb, h->st, ctl.parity, ctl.gen_parity, obs);
 }
@@ -1161,13 +1192,13 @@ static void launch_step_fused(crafter_handle* h, dim3 grid, hipStream_t stream, 
   }
 }
 
-int crafter_step(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
-                 void* stream) {
-  if (ready(h, "crafter_step")) return 1;
-  if (!actions || !reward || !done) return fail(h, "crafter_step: null argument");
-  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+// crafter_step (fin null) and crafter_step_final: one launch sequence.  With fin the step kernels see the pool as off -- every
+// finished env is queued, none adopts a world or draws a frame -- and crafter_requeue_final_kernel walks the queue.
+static int step_launch(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done, void* stream,
+                       const FinalOut* fin) {
   StepCtl ctl;
-  ctl.gen_parity = (h->pool && !h->pool_failed) ? h->gen_parity : -1;
+  const int pool_parity = (h->pool && !h->pool_failed) ? h->gen_parity : -1;
+  ctl.gen_parity = fin ? -1 : pool_parity;
   ctl.safe_seq = h->safe_seq;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   const bool frames = h->cfg.render_obs != 0 && obs != nullptr;
@@ -1207,7 +1238,7 @@ int crafter_step(crafter_handle* h, const int32_t* actions, uint8_t* obs, float*
         if (ea == hipSuccess) ea = hipStreamWaitEvent(h->aux, h->ev_rules, 0);
         if (ea != hipSuccess) return hip_fail(h, "crafter_step: fork to the regeneration stream", ea);
         beside = true;
-        launch_requeue(h, ctl, obs, h->aux, ev[2], ev[3]);
+        launch_requeue(h, ctl, obs, h->aux, ev[2], ev[3], fin, pool_parity);
         ea = hipEventRecord(h->ev_requeue, h->aux);
         if (ea != hipSuccess) return hip_fail(h, "crafter_step: hipEventRecord(regeneration stream)", ea);
       }
@@ -1232,12 +1263,37 @@ int crafter_step(crafter_handle* h, const int32_t* actions, uint8_t* obs, float*
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_step launch", e);
-  if (requeue && !beside) launch_requeue(h, ctl, obs, (hipStream_t)stream, ev[2], ev[3]);
+  if (requeue && !beside) launch_requeue(h, ctl, obs, (hipStream_t)stream, ev[2], ev[3], fin, pool_parity);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_step (auto-reset) launch", e);
   keep_timing_events(h, ev);
   if (h->pool && !h->pool_failed) pool_schedule(h, (hipStream_t)stream);
   return 0;
+}
+
+int crafter_step(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
+                 void* stream) {
+  if (ready(h, "crafter_step")) return 1;
+  if (!actions || !reward || !done) return fail(h, "crafter_step: null argument");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  return step_launch(h, actions, obs, reward, done, stream, nullptr);
+}
+
+int crafter_step_final(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
+                       uint8_t* final_obs, uint8_t* terminated, uint8_t* final_local, float* final_stats, void* stream) {
+  if (ready(h, "crafter_step_final")) return 1;
+  if (!actions || !reward || !done || !terminated) return fail(h, "crafter_step_final: null argument");
+  if (!h->cfg.auto_reset || !h->st.reset_q)
+    return fail(h, "crafter_step_final: the handle has no auto_reset (obs of crafter_step already is the final frame there)");
+  const int lds = h->plan.render_lds > h->plan.reset_lds ? h->plan.render_lds : h->plan.reset_lds;
+  if (symbolic_strip_bytes(h->cfg) > lds) return fail(h, "crafter_step_final: the local view is too large for the kernel's LDS");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  FinalOut fin;
+  fin.obs = h->cfg.render_obs != 0 ? final_obs : nullptr;
+  fin.terminated = terminated;
+  fin.local = final_local;
+  fin.stats = final_stats;
+  return step_launch(h, actions, obs, reward, done, stream, &fin);
 }
 
 int crafter_set_timing(crafter_handle* h, int enable) {

@@ -9,6 +9,7 @@
 #pragma once
 #include "env_core.hpp"
 #include "render.hpp"
+#include "symbolic.hpp"
 #include "worldgen.hpp"
 
 namespace crafter {
@@ -1764,6 +1765,88 @@ __device__ __forceinline__ void render_body(W& w, uint8_t* smem, int env, const 
   r.render(out != nullptr);
   w.sync();
   store_env(e, st, env, !L.frame_over_objs);   // rendering changes no object; the pixel buffer may have reached into the LDS copy
+}
+
+// ---------------------------------------------------------------------------------------------
+// crafter_step_final: the regeneration kernel's body when the caller wants the finished episode's last observation.  The step
+// launch ran with StepCtl::gen_parity = -1, so EVERY env that finished took step_body's will_reset path: its complete terminal
+// state is in global memory, it sits in reset_q and no frame has been drawn for it.  Here, per queued env:
+//   terminated   1 if the player died (env.py:106-115: discount = 1 - dead), 0 if the episode only ran into `length`
+//   final_local / final_stats   crafter_symbolic's pair of the terminal state (one wave: symbolic_body reads global state)
+//   final_obs    env.py:96 obs = self._obs() on the terminal state, night noise from the finished episode's stream included
+//                (engine.py:208-209; the new episode reseeds, env.py:74: nothing of these draws is stored)
+// and then Env.reset as the step kernel / reset_body would have done it: a pooled world if one is ready, else inline.
+struct FinalOut {
+  uint8_t* obs = nullptr;          // [N][size_h][size_w][3] or null
+  uint8_t* terminated = nullptr;   // [N]
+  uint8_t* local = nullptr;        // [N][2][local_gw][local_gh] or null
+  float* stats = nullptr;          // [N][n_items + 4] or null
+};
+
+// The terminal frame: render_body on the state as the step left it, into final_obs, with nothing stored.
+template <class W>
+__device__ __forceinline__ void final_frame_body(W& w, uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb, const StatePtrs& st,
+                                        uint8_t* final_obs) {
+  LdsLayout L = lds_layout(cfg);
+  w.scratch = (uint32_t*)(smem + L.scratch);
+  Env<W> e(w, cfg, tb, smem + L.rules);
+  bind_lds(e, smem, L, st, env);
+  RenderTarget rt = obs_target<W>(cfg, tb, final_obs, env);
+  Renderer<W> r(e, rt, smem + L.render, (uint32_t*)(smem + L.mtb), L.frame_bytes ? smem + L.frame : nullptr);
+  r.preload();
+  load_env(e, st, env, 1);
+  r.render(true);   // daylight[rec.step]: the terminal step's
+}
+
+// Env.reset from the pool under the reset kernels' layout (big_reset_layout: for worlds whose maps stay in global memory the
+// slot table is written in place): reset_body with adopt_world where it generates.
+template <class W, class S = uint16_t>
+__device__ __forceinline__ void adopt_reset_body(W& w, uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb, const StatePtrs& st,
+                                        uint8_t* obs, int gen_parity, int episode) {
+  LdsLayout L = sizeof(S) == 2 ? big_reset_layout(cfg) : lds_layout(cfg, (int)sizeof(S));
+  w.scratch = (uint32_t*)(smem + L.scratch);
+  Env<W, S> e(w, cfg, tb, smem + L.rules);
+  bind_lds<W, -1, S>(e, smem, L, st, env);
+  const bool objs_in_place = L.objs < 0;
+  const bool draw = cfg.render_obs != 0 && obs != nullptr;
+  RenderTarget rt = obs_target<W>(cfg, tb, obs, env);
+  Renderer<W, S> r(e, rt, smem + L.render, (uint32_t*)(smem + L.mtb), L.frame_bytes ? smem + L.frame : nullptr);
+  if (draw) r.preload();   // completes under the barriers below
+  load_env(e, st, env, 0);
+  adopt_world(e, st, env, episode);
+  if (st.pool_stats && w.leader()) w.global_add(st.pool_stats + 0, 1);
+  request_generation(w, cfg, st, gen_parity, env, episode + 2);
+  if (cfg.want_semantic && st.semantic) write_semantic(e, st.semantic, env);
+  if (L.frame_over_objs) store_objs(e, st, env);
+  w.sync();
+  r.render(draw);   // step 0: a day frame
+  w.sync();
+  store_env(e, st, env, !L.frame_over_objs && !objs_in_place);
+}
+
+template <class W>
+__device__ __forceinline__ void final_reset_body(W& w, uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb, const StatePtrs& st,
+                                        uint8_t* obs, int gen_parity, uint32_t safe_seq, int32_t* next_step, const FinalOut& fo) {
+  if (w.leader()) fo.terminated[env] = st.rec[env].dead != 0 ? 1 : 0;
+  if ((fo.local || fo.stats) && w.wave0()) {
+    if (lds_layout(cfg).maps_in_lds)
+      symbolic_body<W, 0>(w, smem, env, cfg, tb, st, nullptr, fo.local, fo.stats);
+    else
+      symbolic_body<W, 1>(w, smem, env, cfg, tb, st, nullptr, fo.local, fo.stats);
+  }
+  w.sync();
+  if (cfg.render_obs != 0 && fo.obs != nullptr) {
+    final_frame_body(w, smem, env, cfg, tb, st, fo.obs);
+    w.sync();
+  }
+  const int next_episode = st.rec[env].episode + 1;
+  if (gen_parity >= 0 && pool_ready<W>(cfg, st, env, next_episode, safe_seq)) {
+    adopt_reset_body<W>(w, smem, env, cfg, tb, st, obs, gen_parity, next_episode);
+    if (next_step && w.leader()) next_step[env] = 1;   // (the new episode's first step: what step_body leaves behind an adoption)
+  } else {
+    if (st.pool_stats && gen_parity >= 0 && w.leader()) w.global_add(st.pool_stats + 1, 1);
+    reset_body<W>(w, smem, env, cfg, tb, st, obs, gen_parity);
+  }
 }
 
 }  // namespace crafter

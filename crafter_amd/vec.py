@@ -5,10 +5,18 @@ trainers expect (numpy in / numpy out, ``step_async`` + ``step_wait``, auto-rese
 No dependency on SB3 / gymnasium (neither is required by the reference, and neither is in this image): the
 class only follows the protocol, so it can be handed to anything that duck-types a VecEnv.
 
-The finished episode's last frame has to be reported, so the wrapped env runs with ``auto_reset=False``
+The finished episode's last frame has to be reported.  By default the wrapped env runs with ``auto_reset=False``
 and finished envs are reset here with one masked ``reset`` (the in-kernel auto-reset of ``BatchedEnv``
 draws the next episode's first frame over it).  ``info`` follows the reference (env.py:108-115):
 inventory / achievements dicts, discount, player_pos, reward (+ semantic when asked for).
+
+``VecEnvView(..., auto_reset=True)`` keeps the in-kernel auto-reset (world pool included) and takes the last frame from
+``BatchedEnv.step(final=True)`` instead: ``terminal_observation`` is ``final_obs``, ``TimeLimit.truncated`` is
+``terminated == 0``, and there is no masked ``reset``.  obs / reward / done and those two are identical to the default mode.
+The host-side info of an env that finished is then put together from what the finished episode left behind: inventory from
+``final_stats``, achievements from the ``terminal`` row, discount from ``terminated``, reward from the step's reward (with
+``reward=False`` the batch returns 0 and so does this entry).  Not reproduced for such an env: ``player_pos`` and
+``semantic`` describe the new episode's first state.
 """
 import numpy as np
 import torch
@@ -20,9 +28,10 @@ from .env import BoxSpace, DiscreteSpace
 class VecEnvView:
 
   def __init__(self, num_envs, area=(64, 64), view=(9, 9), size=(64, 64), reward=True, length=10000, seed=None,
-               seeds=None, device='cuda', semantic=False, **kwargs):
+               seeds=None, device='cuda', semantic=False, auto_reset=False, **kwargs):
+    self._auto_reset = bool(auto_reset)
     self._batch = BatchedEnv(num_envs, area=area, view=view, size=size, reward=reward, length=length, seed=seed,
-                             seeds=seeds, device=device, auto_reset=False, semantic=semantic, **kwargs)
+                             seeds=seeds, device=device, auto_reset=self._auto_reset, semantic=semantic, **kwargs)
     self.num_envs = int(num_envs)
     b = self._batch
     self.observation_space = BoxSpace(0, 255, tuple(b.observation_shape), np.uint8)
@@ -48,12 +57,17 @@ class VecEnvView:
 
   def step_wait(self):
     b = self._batch
-    obs, reward, done, info = b.step(self._pending)
+    obs, reward, done, info = b.step(self._pending, final=self._auto_reset)
     self._pending = None
     b.check_errors()
     rec = b.records()
     obs_h, rew_h = obs.cpu().numpy().copy(), reward.cpu().numpy().copy()
     done_h = done.cpu().numpy().astype(bool)
+    if self._auto_reset and done_h.any():   # what the finished episodes left behind (rows valid where done)
+      final_obs = info['final_obs'].cpu().numpy() if 'final_obs' in info else np.zeros_like(obs_h)
+      terminated = info['terminated'].cpu().numpy().astype(bool)
+      final_stats = info['final_stats'].cpu().numpy()
+      terminal = b.terminal.cpu().numpy()
     pos = info['player_pos'].cpu().numpy().astype(np.int64)
     sem = info['semantic'].cpu().numpy() if self._semantic else None
     infos = []
@@ -69,11 +83,19 @@ class VecEnvView:
       }
       if sem is not None:
         d['semantic'] = sem[i].copy()
-      if done_h[i]:
+      if done_h[i] and self._auto_reset:   # `rec` is the new episode's already
+        dead = bool(terminated[i])
+        d['inventory'] = {n: int(final_stats[i, k]) for k, n in enumerate(b.item_names)}
+        d['achievements'] = {n: int(terminal[i, k]) for k, n in enumerate(b.achievement_names)}
+        d['discount'] = 1 - float(dead)
+        d['reward'] = float(rew_h[i])
+        d['terminal_observation'] = final_obs[i].copy()
+        d['TimeLimit.truncated'] = not dead
+      elif done_h[i]:
         d['terminal_observation'] = obs_h[i].copy()
         d['TimeLimit.truncated'] = not dead   # the episode ran into `length` (env.py:106-107)
       infos.append(d)
-    if done_h.any():
+    if done_h.any() and not self._auto_reset:
       fresh = b.reset(torch.from_numpy(done_h.astype(np.uint8)).to(b.device)).cpu().numpy()
       obs_h[done_h] = fresh[done_h]
     return obs_h, rew_h, done_h, infos

@@ -218,6 +218,26 @@ int crafter_render(crafter_handle* h, const uint8_t* mask, uint8_t* out, void* s
  * no wait for the world pool.  Additive under ABI revision 7: a binding looks it up by name. */
 int crafter_symbolic(crafter_handle* h, const uint8_t* mask, uint8_t* local, float* stats, void* stream);
 
+/* crafter_step on a handle with cfg->auto_reset that also reports, for every env whose `done` byte this step sets, the last
+ * observation of the episode that finished -- what the reference's Env.step returns with done=True before the caller resets
+ * (Gymnasium / SB3: final_observation / terminal_observation):
+ *   final_obs:   uint8 [num_envs][size_h][size_w][3]: env.py:96, self._obs() on the terminal state, with the night noise drawn
+ *                from the FINISHED episode's RNG as the reference draws it (engine.py:208-209; the next episode reseeds,
+ *                env.py:74).  May be NULL; ignored on a handle that draws no frames (cfg->render_obs == 0).
+ *   terminated:  uint8 [num_envs], required: 1 if the player died (env.py:106-115, discount == 0), 0 if the episode only ran
+ *                into `length`; 1 when both happen.
+ *   final_local, final_stats: crafter_symbolic's pair of the terminal state (layouts above; the daylight entry is that of the
+ *                terminal step).  Either may be NULL.
+ * Rows of envs that did not finish in this step are NOT touched: read all four under `done`.  obs, reward, done, the terminal
+ * rows, info['semantic'], every byte of env state after the call and the worlds later episodes get are bit-identical to
+ * crafter_step's; calls of crafter_step, crafter_step_final and crafter_step_n may be mixed freely on one handle.  The step
+ * kernels hand every finished env to a second kernel behind the step launch, which draws the terminal frame, then takes the
+ * env's next world from the pool or regenerates it inline.  On a handle without auto_reset the call fails (there `obs`
+ * already is the final frame).  crafter_step_n and crafter_step_exchange have no final variant.
+ * Additive under ABI revision 7: a binding looks it up by name. */
+int crafter_step_final(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
+                       uint8_t* final_obs, uint8_t* terminated, uint8_t* final_local, float* final_stats, void* stream);
+
 /* Measurement aid (no reference counterpart): when enabled, crafter_step attaches HIP start / stop events to
  * its two kernels (hipExtLaunchKernelGGL: the kernels' own execution time on the launch stream, what a
  * profiler reports).  crafter_get_timing waits for the recorded events, returns the SUM of step-kernel and
