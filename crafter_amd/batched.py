@@ -305,13 +305,123 @@ class BatchedEnv:
                     RuntimeWarning, stacklevel=3)
 
   # ------------------------------------------------------------------ Env API
-  def reset(self, mask=None):
-    """Env.reset() (env.py:70-81) for all envs, or those with a non-zero mask byte.  Returns obs."""
+  def reset(self, mask=None, seeds=None, episodes=None):
+    """Env.reset() (env.py:70-81) for all envs, or those with a non-zero mask byte.  Returns obs.
+    seeds / episodes: reseed(seeds, episodes, mask) first, in the same call -- the named envs start episode `episodes` (1 by
+    default) of `seeds`, the level a fresh crafter.Env(seed=...) shows at that reset().  episodes without seeds: the rows keep
+    their seeds ("restart at episode k")."""
+    if seeds is not None or episodes is not None:
+      kept = self._reseed(seeds, episodes, mask)
+    else:
+      kept = None
     mask, mptr = self._mask(mask)
     with torch.cuda.device(self.device):
       self._check(self._lib.crafter_reset(self._handle, mptr, C.c_void_p(self.obs.data_ptr()), self._stream()))
-    self._keep = mask
+    self._keep = mask if kept is None else (mask, kept)
     return self.obs
+
+  # ------------------------------------------------------------------ levels (include/crafter_hip.h crafter_reseed)
+  MAX_EPISODE = 2 ** 31 - 3   # the world pool asks for episode + 2
+
+  @staticmethod
+  def _check_levels(num_envs, seeds, episodes):
+    """The host side of reseed(), callable without a device: -> (lanes, episodes), each a numpy array (uint64 / int32
+    [num_envs]) made of host values, the device tensor that was given, or None.  Host values are checked here and raise
+    ValueError before anything is enqueued; device tensors are only checked for dtype and shape (never read back)."""
+    def on_device(t):
+      return torch.is_tensor(t) and t.is_cuda
+    lanes = None
+    if on_device(seeds):
+      if seeds.dtype not in (torch.int64, getattr(torch, 'uint64', torch.int64)) or tuple(seeds.shape) != (num_envs,):
+        raise ValueError(f'seeds on the device must be an int64 / uint64 tensor of shape [{num_envs}] (the 64 lane bits)')
+      lanes = seeds
+    elif seeds is not None:
+      seeds = seeds.tolist() if torch.is_tensor(seeds) or isinstance(seeds, np.ndarray) else list(seeds)
+      if len(seeds) != num_envs:
+        raise ValueError(f'len(seeds) is {len(seeds)}, the batch has {num_envs} envs')
+      lanes = state.seed_lanes(seeds)
+    eps = None
+    if on_device(episodes):
+      if episodes.dtype != torch.int32 or tuple(episodes.shape) != (num_envs,):
+        raise ValueError(f'episodes on the device must be an int32 tensor of shape [{num_envs}]')
+      eps = episodes
+    elif episodes is not None:
+      a = np.asarray(episodes.cpu() if torch.is_tensor(episodes) else episodes)
+      if a.ndim == 0:
+        a = np.full(num_envs, a[()])
+      a = a.reshape(-1)
+      if a.size != num_envs:
+        raise ValueError(f'len(episodes) is {a.size}, the batch has {num_envs} envs')
+      if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('episodes must be integers')
+      if a.size and (a.min() < 1 or a.max() > BatchedEnv.MAX_EPISODE):
+        raise ValueError(f'episodes must lie in 1 .. {BatchedEnv.MAX_EPISODE}')
+      eps = a.astype(np.int32)
+    return lanes, eps
+
+  def _reseed(self, seeds, episodes, mask):
+    if not hasattr(self._lib, 'crafter_reseed'):
+      raise _libmod.CrafterLibError('the loaded library has no crafter_reseed (an older build): level selection is not available')
+    if seeds is not None and not (torch.is_tensor(seeds) and seeds.is_cuda):
+      seeds = seeds.tolist() if torch.is_tensor(seeds) or isinstance(seeds, np.ndarray) else list(seeds)
+    lanes, eps = self._check_levels(self.num_envs, seeds, episodes)
+    host_seeds = seeds if isinstance(seeds, list) else None
+    host_mask = None
+    if mask is not None and not (torch.is_tensor(mask) and mask.is_cuda):
+      host_mask = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).reshape(-1) != 0
+    dmask, mptr = self._mask(mask, check_len=True)
+    for t in (lanes, eps):
+      if torch.is_tensor(t) and t.device != self.device:
+        raise ValueError(f'level tensor on {t.device}, batch on {self.device}')
+    with torch.cuda.device(self.device):
+      if lanes is None:   # episodes alone: the rows keep their lanes
+        o = self._off['seed_lane']
+        lanes = self._rec_i32[:, o:o + 2].contiguous().view(torch.int64).reshape(-1)
+      elif torch.is_tensor(lanes):
+        lanes = lanes.contiguous()
+      else:
+        lanes = torch.from_numpy(lanes.view(np.int64)).to(self.device)
+      if eps is not None:
+        eps = eps.contiguous() if torch.is_tensor(eps) else torch.from_numpy(eps).to(self.device)
+      self._check(self._lib.crafter_reseed(self._handle, mptr, C.c_void_p(lanes.data_ptr()),
+                                           None if eps is None else C.c_void_p(eps.data_ptr()), self._stream()))
+    if seeds is not None:   # self.seeds: what the host knows
+      if host_mask is not None:
+        for i in np.nonzero(host_mask)[0]:
+          self.seeds[i] = None if host_seeds is None else host_seeds[i]
+      elif mask is None:
+        self.seeds = [None] * self.num_envs if host_seeds is None else list(host_seeds)
+      elif host_seeds is None:
+        self.seeds = [None] * self.num_envs
+      else:   # a mask on the device is not read back: whether a row took its new seed is only known where that changes nothing
+        self.seeds = [old if old == new else None for old, new in zip(self.seeds, host_seeds)]
+    self._keep = (dmask, lanes, eps)
+    return self._keep
+
+  def reseed(self, seeds, episodes=None, mask=None):
+    """Chooses the level the named envs (mask: non-zero bytes; None: all) play NEXT: their next reset -- reset() or the
+    automatic one -- starts episode `episodes` of `seeds`, exactly what a freshly constructed crafter.Env(seed=...) shows at
+    its episodes-th reset(), and every later episode follows from there.  The episode in progress plays on unchanged; only
+    its number reads episodes - 1 from now on (info['episode'], the terminal row).  Enqueued on the current stream.
+    seeds: a host sequence of num_envs hashables (hashed as the reference hashes its seed: anything it accepts works), or an
+    int64 / uint64 device tensor [num_envs] carrying the 64 lane bits (levels()); entries of unnamed rows are ignored.
+    episodes: None (1), an int, a host sequence or an int32 device tensor [num_envs].  Host values are checked before anything
+    is enqueued (ValueError: wrong length, episode outside 1 .. 2**31 - 3); device tensors are not read back -- the kernel
+    takes an episode below 1 as 1.  self.seeds follows host seeds in the named rows and reads None where a device tensor was
+    given (a mask on the device is not read back either: under one, every row whose seed may have changed reads None).
+    With the world pool running the call brings the pool to rest first and empties the named envs' entries: each regenerates
+    its next world inline once, then the pool serves it again."""
+    if seeds is None:
+      raise ValueError('reseed needs seeds (reset(mask, episodes=...) restarts rows at an episode of their own seeds)')
+    self._reseed(seeds, episodes, mask)
+
+  def levels(self):
+    """-> (seed_lane int64 [N], episode int32 [N]): device copies of each env's seed lane and of the number of the episode it is
+    in, as info() reads them.  reset(seeds=lanes, episodes=episode) on this batch, or on any batch of the same geometry,
+    replays exactly those episodes from their start."""
+    o = self._off['seed_lane']
+    lanes = self._rec_i32[:, o:o + 2].contiguous().view(torch.int64).reshape(-1)
+    return lanes, self._rec_i32[:, self._off['episode']].clone()
 
   def step(self, actions, info=True, out=None, final=False):
     """Env.step() (env.py:83-118) for all envs.  actions: int tensor [N] on the device.

@@ -20,6 +20,7 @@
 #include "dispatch_order.hpp"
 #include "env_copy.hpp"
 #include "env_kernels.hpp"
+#include "env_levels.hpp"
 #include "launch_plan.hpp"
 #include "symbolic.hpp"
 #include "wave_gfx950.hpp"
@@ -353,6 +354,13 @@ crafter_symbolic_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* _
   WS w;
   const int wave = WS::uni((int)(threadIdx.x >> 6));
   symbolic_body<WS, MAP>(w, smem + wave * strip_bytes, (int)blockIdx.x * kSymbolicEnvs + wave, cfg, tb, st, mask, local, stats);
+}
+
+// crafter_reseed (env_levels.hpp): one thread per env edits its record and empties its two pool entries.
+__global__ void __launch_bounds__(kReseedThreads)
+crafter_reseed_kernel(Config cfg, StatePtrs st, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_lane,
+                      const int32_t* __restrict__ episode) {
+  reseed_body<WaveGfx950<kReseedThreads>>((int)(blockIdx.x * kReseedThreads + threadIdx.x), cfg, st, mask, seed_lane, episode);
 }
 
 // Builds the renderer's static block once per table upload (one workgroup).
@@ -1110,6 +1118,22 @@ int crafter_load_envs(crafter_handle* h, const crafter_state_ptrs* store, int32_
   CopySide a{store, store_rows, store_max_objects, store_obs, store_reward, store_done};
   CopySide b{&h->st, h->cfg.num_envs, h->cfg.max_objects, obs, reward, done};
   return launch_copy(h, "crafter_load_envs", COPY_LOAD, a, b, rows, idx, n, (hipStream_t)stream, false);
+}
+
+// Level selection (env_levels.hpp): the named envs' next reset starts episode `episode` of lane `seed_lane`.  The kernel empties
+// their pool entries, so the pool is brought to rest first, exactly as before crafter_load_envs: without that a batch in flight
+// could deliver a world of the old lane into an emptied entry behind the kernel, and a queued request would keep `pending` set.
+// A pool that is off or has failed is not waited for; a failed pool's entries (still bound) are emptied all the same.
+int crafter_reseed(crafter_handle* h, const uint8_t* mask, const uint64_t* seed_lane, const int32_t* episode, void* stream) {
+  if (ready(h, "crafter_reseed")) return 1;
+  if (!seed_lane) return fail(h, "crafter_reseed: null seed_lane");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  pool_quiesce(h, (hipStream_t)stream);
+  hipLaunchKernelGGL(crafter_reseed_kernel, dim3((unsigned)((h->cfg.num_envs + kReseedThreads - 1) / kReseedThreads)), dim3(kReseedThreads), 0,
+                     (hipStream_t)stream, h->cfg, h->st, mask, seed_lane, episode);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_reseed launch", e);
+  return 0;
 }
 
 static int requeue_grid(const crafter_handle* h, const StepCtl& ctl) {

@@ -137,10 +137,21 @@ class Env(BaseClass):
   def action_names(self):
     return self._batch.action_names
 
-  def reset(self):
-    self._episode += 1
-    self._step = 0
-    obs = self._batch.reset()
+  def reset(self, seed=None, episode=None):
+    """Env.reset() (env.py:70-81).  seed (Gymnasium's reset(seed=...)): the env becomes crafter.Env(seed=seed) at its
+    episode-th reset (default 1) -- that level, and the episodes that follow it; _seed and _episode say so, and a deepcopy
+    or pickle taken afterwards carries the new seed.  episode alone restarts the current seed at that episode."""
+    if seed is None and episode is None:
+      self._episode += 1
+      self._step = 0
+      obs = self._batch.reset()
+    else:
+      episode = 1 if episode is None else int(episode)
+      obs = self._batch.reset(seeds=None if seed is None else [seed], episodes=[episode])   # (raises before anything changes)
+      if seed is not None:
+        self._seed = seed
+      self._episode = episode
+      self._step = 0
     self._player = _PlayerView(self)
     out = obs[0].cpu().numpy()
     self._batch.check_errors()

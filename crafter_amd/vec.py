@@ -111,6 +111,25 @@ class VecEnvView:
     """Seeds are fixed at construction (``seed`` / ``seeds``): one RandomState per env, env.py:74."""
     return [None] * self.num_envs
 
+  def reseed(self, seeds, episodes=None, indices=None):
+    """BatchedEnv.reseed for the envs `indices` (all by default): seeds / episodes hold one entry per env named (episodes may be
+    one int for all of them, default 1).  Takes effect at each env's next reset -- the one step_wait() does for it when its
+    episode ends --, which starts episode `episodes` of that seed."""
+    b = self._batch
+    if indices is None:
+      return b.reseed(seeds, episodes)
+    idx = self._indices(indices)
+    seeds = list(seeds)
+    eps = [1 if episodes is None else episodes] * len(idx) if episodes is None or np.isscalar(episodes) else list(episodes)
+    if len(seeds) != len(idx) or len(eps) != len(idx):
+      raise ValueError('seeds and episodes need one entry per env named by indices')
+    if any(not 0 <= i < self.num_envs for i in idx):
+      raise ValueError(f'indices out of range 0 .. {self.num_envs - 1}')
+    full_seeds, full_eps, mask = list(b.seeds), [1] * self.num_envs, np.zeros(self.num_envs, np.uint8)
+    for i, s, e in zip(idx, seeds, eps):
+      full_seeds[i], full_eps[i], mask[i] = s, e, 1
+    return b.reseed(full_seeds, full_eps, mask)
+
   def render(self, size=None, mode='rgb_array'):
     return self._batch.render(size).cpu().numpy()
 

@@ -238,6 +238,26 @@ int crafter_symbolic(crafter_handle* h, const uint8_t* mask, uint8_t* local, flo
 int crafter_step_final(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
                        uint8_t* final_obs, uint8_t* terminated, uint8_t* final_local, float* final_stats, void* stream);
 
+/* Level selection (no reference counterpart as a call: the reference fixes the seed in Env.__init__, env.py:32, and a world is a
+ * pure function of (seed, episode), env.py:74).  For every env whose mask byte is non-zero (mask == NULL: all):
+ *   rec.seed_lane = seed_lane[i];  rec.episode = max(episode[i], 1) - 1;
+ *   both of its world-pool entries are emptied (pool_hdr[0|1][i].ready = 0, .pending = 0);  gen_latest[i] = rec.episode.
+ * All pointers are DEVICE pointers.  mask: uint8 [num_envs] or NULL.  seed_lane: uint64 [num_envs], required: CPython's
+ * hash(seed) as an unsigned 64-bit lane, what crafter_env_rec.seed_lane holds.  episode: int32 [num_envs], or NULL for 1; values
+ * below 1 are taken as 1, and a caller keeps them <= 2^31 - 3 (the pool asks for episode + 2).  Rows with a zero mask byte are not
+ * touched and their seed_lane / episode entries are not read.
+ * Meaning: the env's NEXT reset -- crafter_reset or the automatic one -- starts episode episode[i] of that seed, exactly what a
+ * freshly constructed crafter.Env(seed=...) produces at its episode[i]-th reset(), and every later episode follows from there.
+ * The episode in progress plays on unchanged; only its number reads episode[i] - 1 from then on (info['episode'], the
+ * `terminal` row's episode entry).
+ * Like every other entry point the call only enqueues work.  Before the kernel runs the world pool is brought to rest as before
+ * crafter_load_envs: the requests collected so far are launched as a batch and the stream waits (on the device) for every batch
+ * launched -- otherwise a batch in flight could deliver a world of the old seed into an emptied entry.  The env regenerates its next
+ * world inline once and the pool takes over again.  With the pool off, failed or absent only the record is written (a failed
+ * pool's entries, still bound, are emptied too).
+ * Additive under ABI revision 7: a binding looks it up by name. */
+int crafter_reseed(crafter_handle* h, const uint8_t* mask, const uint64_t* seed_lane, const int32_t* episode, void* stream);
+
 /* Measurement aid (no reference counterpart): when enabled, crafter_step attaches HIP start / stop events to
  * its two kernels (hipExtLaunchKernelGGL: the kernels' own execution time on the launch stream, what a
  * profiler reports).  crafter_get_timing waits for the recorded events, returns the SUM of step-kernel and
