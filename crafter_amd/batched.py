@@ -595,6 +595,32 @@ class BatchedEnv:
     self._keep = mask
     return local, stats
 
+  # ------------------------------------------------------------------ legal-action mask (include/crafter_hip.h crafter_legal_actions)
+  def legal_actions(self, mask=None, out=None):
+    """uint8 [N, num_actions] on the device, in action_names order: legal[e, a] = 1 iff Player.update (objects.py:99-131), run
+    on env e's current state with action a, passes every guard of that action's branch.  With target = pos + facing and
+    awake = not (sleeping and energy < max): noop always; move_* iff awake and the destination is inside the world, free of
+    objects and walkable for the player (iff the position would change: a blocked move still turns and is not legal); do iff
+    awake and target holds a zombie, skeleton, cow or ripe plant, or no object and water or a material whose collect rule's
+    `require` the inventory holds; sleep iff not sleeping and energy < max; place_* iff awake, target free of objects, its
+    material in `where` and `uses` in the inventory; make_* iff awake, every `nearby` material in the 3 x 3 window (numpy's
+    slices: empty at x == 0 or y == 0) and `uses` in the inventory.  For every action but a move, 0 means the step does what
+    noop does.  The guards are this batch's `rules`.
+    After a step() that auto-reset an env the row describes the new episode's first state, after a rollout() the state behind
+    its last step.  Read-only: no draw from the envs' RNG, no byte of state changes.  mask: rows with a zero byte are left
+    untouched.  out: a contiguous uint8 device tensor of exactly that shape to write into."""
+    shape = (self.num_envs, self.num_actions)
+    if out is None:
+      out = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.uint8 and
+              tuple(out.shape) == shape and out.is_contiguous()):
+      raise ValueError(f'out must be a contiguous torch.uint8 tensor of shape {shape} on {self.device}')
+    mask, mptr = self._mask(mask, check_len=True)
+    with torch.cuda.device(self.device):
+      self._check(self._lib.crafter_legal_actions(self._handle, mptr, C.c_void_p(out.data_ptr()), self._stream()))
+    self._keep = mask
+    return out
+
   def info(self):
     """Device-tensor views of what the reference puts into ``info`` (env.py:108-115)."""
     o, r = self._off, self._rec_i32

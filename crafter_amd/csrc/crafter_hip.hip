@@ -22,6 +22,7 @@
 #include "env_kernels.hpp"
 #include "env_levels.hpp"
 #include "launch_plan.hpp"
+#include "legal.hpp"
 #include "symbolic.hpp"
 #include "wave_gfx950.hpp"
 
@@ -354,6 +355,17 @@ crafter_symbolic_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* _
   WS w;
   const int wave = WS::uni((int)(threadIdx.x >> 6));
   symbolic_body<WS, MAP>(w, smem + wave * strip_bytes, (int)blockIdx.x * kSymbolicEnvs + wave, cfg, tb, st, mask, local, stats);
+}
+
+// crafter_legal_actions (legal.hpp): one wave per env, kLegalEnvs envs per workgroup, no LDS and no barrier: the waves of the
+// batch tail and of masked rows leave at once.  MAP as for crafter_symbolic_kernel.
+template <int MAP>
+__global__ void __launch_bounds__(kLegalThreads)
+crafter_legal_actions_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, uint8_t* __restrict__ legal) {
+  typedef WaveGfx950<kLegalThreads> WL;
+  WL w;
+  const int wave = WL::uni((int)(threadIdx.x >> 6));
+  legal_body<WL, MAP>(w, (int)blockIdx.x * kLegalEnvs + wave, cfg, tb, st, mask, legal);
 }
 
 // crafter_reseed (env_levels.hpp): one thread per env edits its record and empties its two pool entries.
@@ -1485,6 +1497,22 @@ int crafter_symbolic(crafter_handle* h, const uint8_t* mask, uint8_t* local, flo
                        symbolic_strip_bytes(h->cfg));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_symbolic launch", e);
+  return 0;
+}
+
+// The legal-action mask of the state as it stands on `stream` (legal.hpp).  Like crafter_symbolic it reads live rows only and
+// waits for no batch of the pool.
+int crafter_legal_actions(crafter_handle* h, const uint8_t* mask, uint8_t* legal, void* stream) {
+  if (ready(h, "crafter_legal_actions")) return 1;
+  if (!legal) return fail(h, "crafter_legal_actions: null output");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  const dim3 grid((unsigned)((h->cfg.num_envs + kLegalEnvs - 1) / kLegalEnvs)), block(kLegalThreads);
+  if (h->plan.maps_in_lds)
+    hipLaunchKernelGGL(crafter_legal_actions_kernel<0>, grid, block, 0, (hipStream_t)stream, h->cfg, h->tb, h->st, mask, legal);
+  else
+    hipLaunchKernelGGL(crafter_legal_actions_kernel<1>, grid, block, 0, (hipStream_t)stream, h->cfg, h->tb, h->st, mask, legal);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_legal_actions launch", e);
   return 0;
 }
 

@@ -195,3 +195,7 @@ class Env(BaseClass):
     """BatchedEnv.symbolic() for this env: (local uint8 [2, gw, gh], stats float32 [n_items + 4]) as numpy arrays."""
     local, stats = self._batch.symbolic()
     return local[0].cpu().numpy(), stats[0].cpu().numpy()
+
+  def legal_actions(self):
+    """BatchedEnv.legal_actions() for this env: bool [n_actions], True where the action passes its guards in the current state."""
+    return self._batch.legal_actions()[0].cpu().numpy().astype(bool)

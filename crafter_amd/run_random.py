@@ -1,6 +1,7 @@
 """``python -m crafter_amd.run_random`` -- the reference's ``crafter/run_random.py`` (lines 10-44) on the
 MI355X path: same flags, same prints (reset time, material counts, step time / FPS, episode length).
-``--envs N`` (not in the reference) runs N environments at once through BatchedEnv."""
+``--envs N`` (not in the reference) runs N environments at once through BatchedEnv; ``--legal`` (not in the reference either)
+samples uniformly among the actions the legal-action mask allows instead of among all of them."""
 import argparse
 import copy
 import time
@@ -8,7 +9,14 @@ import time
 import numpy as np
 
 
-def main():
+def sample_legal(legal, generator=None):
+  """One action per row of the mask `legal` (uint8 / bool [N, n_actions] tensor), uniform among the row's non-zero entries
+  (noop is always one) -> int32 [N] on the mask's device."""
+  import torch
+  return torch.multinomial(legal.to(torch.float32), 1, generator=generator).reshape(-1).to(torch.int32)
+
+
+def main(argv=None):
   parser = argparse.ArgumentParser()
   parser.add_argument('--seed', type=int, default=None)
   parser.add_argument('--area', nargs=2, type=int, default=(64, 64))
@@ -17,7 +25,8 @@ def main():
   parser.add_argument('--record', type=str, default=None)
   parser.add_argument('--episodes', type=int, default=1)
   parser.add_argument('--envs', type=int, default=1)
-  args = parser.parse_args()
+  parser.add_argument('--legal', action='store_true', help='sample uniformly among the legal actions (BatchedEnv.legal_actions)')
+  args = parser.parse_args(argv)
 
   import torch
   from . import BatchedEnv, Env, tables
@@ -27,10 +36,16 @@ def main():
   rules['items']['health']['initial'] = args.health
   random = np.random.RandomState(args.seed)
 
+  def legal_generator(device):   # --legal: torch.multinomial's stream, on the device the mask lives on
+    generator = torch.Generator(device=device)
+    generator.manual_seed(0 if args.seed is None else args.seed)
+    return generator
+
   if args.envs == 1:
     env = Env(area=tuple(args.area), length=args.length, seed=args.seed, rules=rules)
     if args.record:   # run_random.py:24: crafter.Recorder(env, args.record) -> stats.jsonl
       env = EnvStatsRecorder(env, args.record)
+    generator = legal_generator('cpu') if args.legal else None
     for _ in range(args.episodes):
       start = time.time()
       env.reset()
@@ -42,7 +57,10 @@ def main():
       start = time.time()
       done = False
       while not done:
-        action = random.randint(0, env.action_space.n)
+        if args.legal:
+          action = int(sample_legal(torch.from_numpy(env.legal_actions()[None]), generator)[0])
+        else:
+          action = random.randint(0, env.action_space.n)
         _, _, done, _ = env.step(action)
       duration = time.time() - start
       step = env._step
@@ -54,6 +72,7 @@ def main():
   env = BatchedEnv(args.envs, area=tuple(args.area), length=args.length, seed=seed, rules=rules, auto_reset=True)
   if args.record:
     env = BatchedStatsRecorder(env, args.record)
+  generator = legal_generator(env.device) if args.legal else None
   start = time.time()
   env.reset()
   torch.cuda.synchronize()
@@ -61,7 +80,10 @@ def main():
   finished, steps = 0, 0
   start = time.time()
   while finished < args.episodes * args.envs:
-    actions = torch.from_numpy(random.randint(0, env.num_actions, size=args.envs).astype(np.int32)).to(env.device)
+    if args.legal:
+      actions = sample_legal(env.legal_actions(), generator)
+    else:
+      actions = torch.from_numpy(random.randint(0, env.num_actions, size=args.envs).astype(np.int32)).to(env.device)
     _, _, done, _ = env.step(actions, info=False)
     finished += int(done.sum())
     steps += args.envs

@@ -147,7 +147,17 @@ class VecEnvView:
   def set_attr(self, attr_name, value, indices=None):
     raise AttributeError('the batched env has no per-env Python attributes to set')
 
+  def action_masks(self):
+    """bool [num_envs, n_actions]: BatchedEnv.legal_actions() of the states the next step() acts on (the SB3-contrib
+    ``action_masks`` protocol of mask-aware trainers)."""
+    return self._batch.legal_actions().cpu().numpy().astype(bool)
+
   def env_method(self, method_name, *args, indices=None, **kwargs):
+    """``env_method('action_masks', indices=...)`` -> the list of rows SB3-contrib's ``get_action_masks`` stacks; there are
+    no per-env Python objects to call anything else on."""
+    if method_name == 'action_masks' and not args and not kwargs:
+      masks = self.action_masks()
+      return [masks[i] for i in self._indices(indices)]
     raise AttributeError('the batched env has no per-env Python objects to call')
 
   def env_is_wrapped(self, wrapper_class, indices=None):

@@ -218,6 +218,34 @@ int crafter_render(crafter_handle* h, const uint8_t* mask, uint8_t* out, void* s
  * no wait for the world pool.  Additive under ABI revision 7: a binding looks it up by name. */
 int crafter_symbolic(crafter_handle* h, const uint8_t* mask, uint8_t* local, float* stats, void* stream);
 
+/* The legal-action mask of the state as it stands (no reference counterpart as a call; every value is the reference's), for
+ * masked envs (NULL: all; rows with a zero mask byte are left untouched).
+ *   legal: uint8 [num_envs][n_actions], required, in the action order of the uploaded rules (crafter_rules.action_kind / _arg).
+ *     legal[e][a] = 1 iff Player.update (objects.py:99-131), run on env e's current state with action a, passes every guard of
+ *     that action's branch.  target = pos + facing; (material, obj) = world[target], (None, None) outside the world;
+ *     awake = not (sleeping and energy < max) (objects.py:103-108; a sleeping player with full energy wakes up and its action
+ *     counts normally):
+ *       noop     always
+ *       move_*   (objects.py:174-179, 36-47) awake, and the destination cell is inside the world, holds no object and its
+ *                material is in player_walkable_mask: legal iff the player's position would change (a blocked move still
+ *                turns the player and is NOT legal)
+ *       do       an object on target (objects.py:181-212): awake, and it is a zombie, skeleton or cow, or a plant with
+ *                grown > 300 (an arrow or an unripe plant gives 0); none (objects.py:214-229): awake, and material is water or
+ *                collect[material].valid with every `require` amount in the inventory (the `probability` draw is no guard)
+ *       sleep    (objects.py:117-119) not sleeping and energy < max
+ *       place_*  (objects.py:231-249) awake, no object on target, where_mask has material's bit, every `uses` amount in the
+ *                inventory
+ *       make_*   (objects.py:251-261) awake, nearby_mask within the materials of World.nearby(pos, 1), every `uses` amount in
+ *                the inventory; the window has numpy's slice semantics (engine.py:95-98): EMPTY when x == 0 or y == 0, clipped
+ *                at W - 1 / H - 1
+ *     For every action but a move, legal == 0 means the step does exactly what noop does (map, objects, inventory,
+ *     achievements, counters, RNG stream).  The guards are read from the uploaded crafter_rules.  The state is read as it
+ *     stands: no special treatment of a dead player or of a finished env without auto-reset.
+ * Read-only: no draw from the env's RNG, no byte of state changes.  Reads live rows only: no wait for the world pool.  Only
+ * enqueues work; returns 0, or non-zero with crafter_last_error (legal == NULL is an error).  Additive under ABI revision 7:
+ * a binding looks it up by name. */
+int crafter_legal_actions(crafter_handle* h, const uint8_t* mask, uint8_t* legal, void* stream);
+
 /* crafter_step on a handle with cfg->auto_reset that also reports, for every env whose `done` byte this step sets, the last
  * observation of the episode that finished -- what the reference's Env.step returns with done=True before the caller resets
  * (Gymnasium / SB3: final_observation / terminal_observation):
