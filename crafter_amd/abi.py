@@ -29,7 +29,7 @@ STATUS_NAMES = {
     ST_CHUNK_OVERFLOW: 'chunk table overflow',
     ST_POOL_MISMATCH: 'world pool handed out the wrong episode',
     ST_PIPE_STALL: 'a bounded in-kernel wait ran out (reserved)',
-    ST_BAD_COPY: 'ST_BAD_COPY: copy_envs / load_state refused its indices (out of range, duplicate or overlapping destination); nothing was copied',
+    ST_BAD_COPY: 'ST_BAD_COPY: copy_envs / load_state / step_envs refused its indices (out of range, duplicate or overlapping destination); nothing was copied or stepped',
 }
 
 # texture slots of TablePtrs.tex_tile (crafter_hip_types.h CRAFTER_TEX_*)

@@ -453,6 +453,41 @@ class BatchedEnv:
     self._keep = (actions, obs, reward, done)
     return obs, reward, done, (self.info() if info else {})
 
+  def step_envs(self, idx, actions, info=True, out=None):
+    """step() for the envs idx names and for no other (crafter_step_envs): a tree search steps its scratch rows, an actor loop
+    the envs whose action is ready.  idx: n env indices, 1 <= n <= N, none twice; actions: n ints, actions[i] for env idx[i].
+    Returns (obs, reward, done, info) as step() does -- the full [N] tensors, of which only rows idx are new; every other row,
+    of the state too, is neither read nor written.  For a named env the call is exactly step(): auto-reset, pool, terminal
+    row and info['semantic'] included, and the two may be mixed freely, with rollout() and the copies too.  The launch costs
+    what a batch of n envs costs.
+    Host indices (lists, numpy, CPU tensors) are range- and duplicate-checked here and raise ValueError before anything is
+    enqueued; a device tensor is checked on the device: a bad list refuses the whole call -- no row changes -- and
+    check_errors() raises (ST_BAD_COPY).  out: as for step().  An empty idx enqueues nothing."""
+    if not hasattr(self._lib, 'crafter_step_envs'):
+      raise _libmod.CrafterLibError('the loaded library has no crafter_step_envs (an older build): step_envs is not available')
+    i, hi = self._index(idx, self.num_envs, 'idx')
+    if hi is not None and len(np.unique(hi)) != len(hi):
+      raise ValueError('idx names an env twice')
+    actions = self._actions(actions).reshape(-1)
+    if actions.numel() != i.numel():
+      raise ValueError(f'actions has {actions.numel()} entries, idx names {i.numel()} envs')
+    if i.numel() > self.num_envs:
+      raise ValueError(f'idx names {i.numel()} envs, the batch has {self.num_envs}')
+    obs, reward, done = self.obs, self.reward, self.done
+    if out is not None:
+      obs = obs if out[0] is None else out[0]
+      reward, done = out[1], out[2]
+      self._check_out(obs, self.obs), self._check_out(reward, self.reward), self._check_out(done, self.done)
+    if i.numel():
+      if self._unbounded:
+        self._grow_daylight(1)
+      with torch.cuda.device(self.device):
+        self._check(self._lib.crafter_step_envs(
+            self._handle, C.c_void_p(i.data_ptr()), int(i.numel()), C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
+            C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), self._stream()))
+      self._keep = (i, actions, obs, reward, done)
+    return obs, reward, done, (self.info() if info else {})
+
   def final_buffers(self):
     """The persistent device tensors step(final=True) writes and returns in its info dict: {'final_obs' (absent with
     render=False), 'terminated', 'final_local', 'final_stats'}; allocated at first use, zero-initialised."""

@@ -17,6 +17,7 @@
 
 #include "../../include/crafter_hip.h"
 #include "crafter_rollout.hpp"
+#include "crafter_subset.hpp"
 #include "dispatch_order.hpp"
 #include "env_copy.hpp"
 #include "env_kernels.hpp"
@@ -543,6 +544,7 @@ struct crafter_handle {
   int32_t* copy_mark = nullptr;
   int32_t* copy_verdict = nullptr;
   int32_t copy_stamp = 0;
+  int32_t* subset_actions = nullptr;   // crafter_step_envs: [N] the call's actions scattered to their envs' rows (step_body reads actions[env])
   // optional per-kernel timing (HIP events on the launch stream)
   bool timing = false;
   std::vector<hipEvent_t> events;   // triples: before step, between, after reset
@@ -653,6 +655,12 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
     hipError_t er = rollout_allow_lds(h->plan.render_lds);   // the rollout kernels live in crafter_rollout.hip
     if (er != hipSuccess) {
       std::string msg = std::string("crafter_create: hipFuncSetAttribute(rollout kernels): ") + hipGetErrorString(er);
+      delete h;
+      return fail(nullptr, msg);
+    }
+    er = subset_allow_lds(h->plan.render_lds);   // ... and crafter_step_envs' in crafter_subset.hip
+    if (er != hipSuccess) {
+      std::string msg = std::string("crafter_create: hipFuncSetAttribute(subset kernels): ") + hipGetErrorString(er);
       delete h;
       return fail(nullptr, msg);
     }
@@ -1052,12 +1060,10 @@ static void pool_quiesce(crafter_handle* h, hipStream_t stream) {
   pool_wait_all(h, stream, "hipStreamWaitEvent(copy)");
 }
 
-// The index check, then the copy (env_copy.hpp).  pool_rows: the pool is at rest and both sides are the bound state.
-static int launch_copy(crafter_handle* h, const char* who, int mode, const CopySide& a, const CopySide& b, const int32_t* sidx,
-                       const int32_t* didx, int n, hipStream_t stream, bool pool_rows) {
-  CopyPlan plan;
-  if (!make_copy_plan(plan, h->cfg, a, b, mode, !h->plan.maps_in_lds, (size_t)h->cfg.size_w * h->cfg.size_h * 3, pool_rows))
-    return fail(h, std::string(who) + ": too many buffers for one copy plan");
+// The scratch of an index check on the device (crafter_copy_check_kernel, crafter_step_envs_check_kernel): one mark per row of
+// the bound state and the verdict word, allocated on first use; *stamp: this call's number in the marks, which are cleared
+// only when the numbers start again.
+static int index_check_scratch(crafter_handle* h, const char* who, hipStream_t stream, int32_t* stamp) {
   if (!h->copy_mark) {
     hipError_t ea = hipMalloc((void**)&h->copy_mark, ((size_t)h->cfg.num_envs + 1) * sizeof(int32_t));
     if (ea != hipSuccess) return hip_fail(h, who, ea);
@@ -1070,7 +1076,18 @@ static int launch_copy(crafter_handle* h, const char* who, int mode, const CopyS
     if (em != hipSuccess) return hip_fail(h, who, em);
     h->copy_stamp = 0;
   }
-  const int32_t stamp = ++h->copy_stamp;
+  *stamp = ++h->copy_stamp;
+  return 0;
+}
+
+// The index check, then the copy (env_copy.hpp).  pool_rows: the pool is at rest and both sides are the bound state.
+static int launch_copy(crafter_handle* h, const char* who, int mode, const CopySide& a, const CopySide& b, const int32_t* sidx,
+                       const int32_t* didx, int n, hipStream_t stream, bool pool_rows) {
+  CopyPlan plan;
+  if (!make_copy_plan(plan, h->cfg, a, b, mode, !h->plan.maps_in_lds, (size_t)h->cfg.size_w * h->cfg.size_h * 3, pool_rows))
+    return fail(h, std::string(who) + ": too many buffers for one copy plan");
+  int32_t stamp = 0;
+  if (index_check_scratch(h, who, stream, &stamp)) return 1;
   hipLaunchKernelGGL(crafter_copy_check_kernel, dim3(1), dim3(kCheckThreads), 0, stream, sidx, didx, n, a.rows, b.rows, mode, stamp,
                      h->copy_mark, h->copy_verdict, (EnvRec*)h->st.rec, h->cfg.num_envs);
   hipLaunchKernelGGL(crafter_copy_envs_kernel, dim3((unsigned)((long long)n * plan.parts)), dim3(kCopyThreads), 0, stream, plan, sidx,
@@ -1330,6 +1347,59 @@ int crafter_step_final(crafter_handle* h, const int32_t* actions, uint8_t* obs, 
   fin.local = final_local;
   fin.stats = final_stats;
   return step_launch(h, actions, obs, reward, done, stream, &fin);
+}
+
+// Env.step for the n envs idx names, and for no other: the index check (which scatters the actions to their envs' rows), then
+// n workgroups of the plan's instance (crafter_subset.hip), then the regeneration kernel as behind crafter_step.  One call is
+// one step to the world pool's schedule: an env steps at most once per call.
+int crafter_step_envs(crafter_handle* h, const int32_t* idx, int32_t n, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
+                      void* stream) {
+  if (ready(h, "crafter_step_envs")) return 1;
+  if (n < 0 || n > h->cfg.num_envs) return fail(h, "crafter_step_envs: n outside 0 .. num_envs");
+  if (n == 0) return 0;
+  if (!idx) return fail(h, "crafter_step_envs: null index list");
+  if (!actions || !reward || !done) return fail(h, "crafter_step_envs: null argument");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  if (!h->subset_actions) {
+    hipError_t ea = hipMalloc((void**)&h->subset_actions, (size_t)h->cfg.num_envs * sizeof(int32_t));
+    if (ea != hipSuccess) return hip_fail(h, "crafter_step_envs: actions scratch", ea);
+    h->owned.push_back(h->subset_actions);
+  }
+  StepCtl ctl;
+  ctl.gen_parity = (h->pool && !h->pool_failed) ? h->gen_parity : -1;
+  ctl.safe_seq = h->safe_seq;
+  ctl.early_frame = 0;             // (no early-frame kernel for subsets: launch_plan.hpp choose_step_envs)
+  ctl.next_step = h->next_step;    // an ordered handle: the named envs' entries stay current; the launch follows no order and builds none
+  const bool frames = h->cfg.render_obs != 0 && obs != nullptr;
+  const StepEnvsKernel kernel = choose_step_envs(h->plan, n, frames, h->wide);
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (frames) {   // night frames take their noise from states generated ahead, as in crafter_step
+    if (need_noise_raw(h, "crafter_step_envs: noise scratch")) return 1;
+    ctl.noise_raw = h->noise_raw;
+  }
+  if (h->plan.night_px) {
+    if (frames && need_night_px(h, "crafter_step_envs: night frame scratch")) return 1;
+    ctl.night_px = h->night_px;
+  }
+  SubsetCheck chk;
+  chk.idx = idx; chk.actions = actions; chk.n = n;
+  if (index_check_scratch(h, "crafter_step_envs", (hipStream_t)stream, &chk.stamp)) return 1;
+  chk.mark = h->copy_mark; chk.verdict = h->copy_verdict; chk.rec = (EnvRec*)h->st.rec; chk.rows = h->cfg.num_envs;
+  chk.scattered = h->subset_actions;
+  if (timing_events(h, ev, "crafter_step_envs: hipEventCreate (timing mode)")) return 1;
+  ctl.parity = (int)(h->steps++ & 1);   // (the reset_q halves alternate over every launch that uses them)
+  // timing mode: the step time of the call runs from the check's start to the subset kernel's end
+  launch_step_envs_check(chk, (hipStream_t)stream, ev[0], nullptr);
+  launch_step_subset(kernel, h->plan.instance, n, (size_t)h->plan.step_lds, (hipStream_t)stream, nullptr, ev[1], h->cfg, h->tb, h->st, idx,
+                     h->copy_verdict, h->subset_actions, obs, reward, done, ctl);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_step_envs launch", e);
+  if (h->cfg.auto_reset != 0) launch_requeue(h, ctl, obs, (hipStream_t)stream, ev[2], ev[3]);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_step_envs (auto-reset) launch", e);
+  keep_timing_events(h, ev);
+  if (h->pool && !h->pool_failed) pool_schedule(h, (hipStream_t)stream);
+  return 0;
 }
 
 int crafter_set_timing(crafter_handle* h, int enable) {

@@ -5,6 +5,7 @@
 //
 //   launch_plan()          per handle: crafter_create (rules unknown yet), again in crafter_upload_tables (rules known)
 //   choose_step()          per crafter_step call: which of the step kernels of the plan's instance
+//   choose_step_envs()     per crafter_step_envs call: which of the subset kernels
 //   step_early_frame()     per call: StepCtl::early_frame
 //   keeps_dispatch_order() per handle: whether the launches are ordered slow envs first
 #pragma once
@@ -120,6 +121,22 @@ inline StepKernel choose_step(const LaunchPlan& p, int num_envs, bool frames, bo
   if (!frames) return kStepFused;
   if (!ordered && (wide < 0 ? num_envs <= kWideMaxEnvs : wide != 0)) return kStepWide;
   return step_early_frame(num_envs, early) ? kStepEarly : kStepFused;
+}
+
+// The kernels one crafter_step_envs can launch (crafter_subset.hip): n workgroups, one per named env.
+enum StepEnvsKernel {
+  kSubsetFused,   // crafter_step_subset_kernel<LM, GEO, RUL> of the plan's instance
+  kSubsetWide,    // crafter_step_subset_wide_kernel: 512 threads per env, at most two named envs per CU
+};
+
+// n: the envs the call names (what fills the chip is the launch, not the batch); frames, wide: as for choose_step.
+// No split pair and no early-frame kernel for subsets (StepCtl::early_frame is 0): the measurements behind those two were
+// made for launches that fill the chip -- the pair wins only where no frame is drawn over a whole batch, the early frame from
+// 2048 workgroups on -- and a subset launch is the case where few workgroups run.  No dispatch order either: the launch
+// follows none and builds none (it keeps StepCtl::next_step current for the full launches that do).
+inline StepEnvsKernel choose_step_envs(const LaunchPlan& p, int n, bool frames, int wide) {
+  if (p.instance != kInstance111 || !frames) return kSubsetFused;
+  return (wide < 0 ? n <= kWideMaxEnvs : wide != 0) ? kSubsetWide : kSubsetFused;
 }
 
 // Whether a handle orders its launches, slow envs first (crafter_handle::order).  order_env: CRAFTER_ORDER, -1 unset,

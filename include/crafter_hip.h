@@ -266,6 +266,32 @@ int crafter_legal_actions(crafter_handle* h, const uint8_t* mask, uint8_t* legal
 int crafter_step_final(crafter_handle* h, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
                        uint8_t* final_obs, uint8_t* terminated, uint8_t* final_local, float* final_stats, void* stream);
 
+/* crafter_step for a chosen subset of the batch (no reference counterpart: the reference is one env per process; a tree search
+ * that stepped scratch rows of a batch, or an actor loop that steps whichever envs have an action ready, would otherwise step
+ * every other env too).
+ *   idx:     device int32[n], 1 <= n <= num_envs: the envs to step.  Every entry in range, no env named twice.
+ *   actions: device int32[n]: actions[i] is the action of env idx[i].
+ *   obs, reward, done: the layout of crafter_step -- full [num_envs] rows; obs may be NULL.
+ * For every named env the call is exactly crafter_step for that env: its state, its obs / reward / done row, its terminal row,
+ * info['semantic'], the auto-reset from the pool or through the regeneration kernel behind the launch, and its requests to the
+ * pool.  Rows of envs that are not named are neither read nor written, in the bound state or in obs / reward / done.
+ * n == 0 returns 0 and enqueues nothing; idx == NULL, n < 0 and n > num_envs are errors (crafter_last_error).
+ * The index list is checked on the device before any env steps, like the copy calls' indices: an entry out of range or an env
+ * named twice (two workgroups would step it at once) refuses the WHOLE call -- no row changes -- and sets CRAFTER_ST_BAD_COPY in
+ * the status of the named rows that exist (row 0 if none exists).
+ * The launch is n workgroups, each fetching its env from idx: it costs what a batch of n envs costs, plus the one-workgroup
+ * check in front of it.  crafter_step, crafter_step_envs, crafter_step_final, crafter_step_n and the
+ * copy calls may be mixed freely on one handle.  On a handle that keeps a dispatch order the subset launch follows none and
+ * builds none; it keeps the named envs' entries of the order's input current.
+ * World pool: one call counts as ONE step of the pool's batch period, however few envs it names.  An env steps at most once per
+ * call, so the pool's latency assumption -- every env's worlds are requested two episodes ahead -- holds in that env's own
+ * steps: a loop of small subsets launches batches more often per env-step than a loop of full steps, never less often.
+ * crafter_set_timing attaches its events to this launch as to a step (step time: from the check's start to the subset kernel's
+ * end).  There is no `final` variant and no exchange variant of this call.
+ * Additive under ABI revision 7: a binding looks it up by name. */
+int crafter_step_envs(crafter_handle* h, const int32_t* idx, int32_t n, const int32_t* actions,
+                      uint8_t* obs, float* reward, uint8_t* done, void* stream);
+
 /* Level selection (no reference counterpart as a call: the reference fixes the seed in Env.__init__, env.py:32, and a world is a
  * pure function of (seed, episode), env.py:74).  For every env whose mask byte is non-zero (mask == NULL: all):
  *   rec.seed_lane = seed_lane[i];  rec.episode = max(episode[i], 1) - 1;
