@@ -132,6 +132,7 @@ class BatchedEnv:
     with torch.cuda.device(self.device):
       self._alloc_state()
     self._pool_warned = False
+    self._levels = None   # set_levels: the level table's device tensors
     self.grow_objects = bool(grow_objects)   # check_errors() doubles the slot table before an env can fill it (_grow_objects)
     # Env(length=None): no episode may outrun the daylight table (_grow_daylight).  _step_bound >= every env's step counter.
     self._unbounded = self.cfg.length == 0
@@ -298,6 +299,8 @@ class BatchedEnv:
     if getattr(self, '_timing_on', False):   # handle-level settings move with the handle
       with torch.cuda.device(self.device):
         self._check(self._lib.crafter_set_timing(self._handle, 1))
+    if getattr(self, '_levels', None) is not None:   # ... and so does the level table
+      self._enqueue_levels()
     if was_default:
       import warnings
       warnings.warn(f'crafter_amd: an environment holds more than 192 objects: the slot tables grow to {new_max} entries and the batch '
@@ -418,10 +421,140 @@ class BatchedEnv:
   def levels(self):
     """-> (seed_lane int64 [N], episode int32 [N]): device copies of each env's seed lane and of the number of the episode it is
     in, as info() reads them.  reset(seeds=lanes, episodes=episode) on this batch, or on any batch of the same geometry,
-    replays exactly those episodes from their start."""
+    replays exactly those episodes from their start.
+    With a level table set (set_levels) the pair is (table seed lane, table episode) of level_ids(): the levels actually
+    played, and the promise still holds for reset(seeds=lanes, episodes=episode) on a batch WITHOUT a table.  As for
+    level_ids(), a row is exact if its episode in progress began while this table was set."""
+    if getattr(self, '_levels', None) is not None:
+      ids = self.level_ids().to(torch.int64)
+      return self._levels['lanes'][ids], self._levels['episodes'][ids]
     o = self._off['seed_lane']
     lanes = self._rec_i32[:, o:o + 2].contiguous().view(torch.int64).reshape(-1)
     return lanes, self._rec_i32[:, self._off['episode']].clone()
+
+  # ------------------------------------------------------------------ level sets (include/crafter_hip.h crafter_set_levels)
+  MAX_LEVELS = state.MAX_LEVELS
+
+  @staticmethod
+  def _check_level_set(seeds, episodes, weights, key):
+    """The host side of set_levels(), callable without a device: -> (lanes, episodes, cum, key).  lanes: uint64 numpy [K] or the
+    device tensor given; episodes: int32 numpy [K], the device tensor given, or None (1); cum: uint32 numpy [K] or None; key:
+    the 64 key bits.  Host values are checked here and raise ValueError before anything is enqueued; device tensors are only
+    checked for dtype and shape."""
+    def on_device(t):
+      return torch.is_tensor(t) and t.is_cuda
+    if on_device(seeds):
+      if seeds.dtype not in (torch.int64, getattr(torch, 'uint64', torch.int64)) or seeds.dim() != 1:
+        raise ValueError('seeds on the device must be a one-dimensional int64 / uint64 tensor (the 64 lane bits)')
+      lanes, K = seeds, int(seeds.shape[0])
+    else:
+      seeds = seeds.tolist() if torch.is_tensor(seeds) or isinstance(seeds, np.ndarray) else list(seeds)
+      lanes, K = state.seed_lanes(seeds), len(seeds)
+    if not 1 <= K <= BatchedEnv.MAX_LEVELS:
+      raise ValueError(f'a level table holds 1 .. {BatchedEnv.MAX_LEVELS} levels, got {K}')
+    eps = None
+    if on_device(episodes):
+      if episodes.dtype != torch.int32 or tuple(episodes.shape) != (K,):
+        raise ValueError(f'episodes on the device must be an int32 tensor of shape [{K}]')
+      eps = episodes
+    elif episodes is not None:
+      a = np.asarray(episodes.cpu() if torch.is_tensor(episodes) else episodes)
+      if a.ndim == 0:
+        a = np.full(K, a[()])
+      a = a.reshape(-1)
+      if a.size != K:
+        raise ValueError(f'len(episodes) is {a.size}, the table has {K} levels')
+      if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('episodes must be integers')
+      if a.min() < 1 or a.max() > BatchedEnv.MAX_EPISODE:
+        raise ValueError(f'episodes must lie in 1 .. {BatchedEnv.MAX_EPISODE}')
+      eps = a.astype(np.int32)
+    cum = None
+    if weights is not None:
+      w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights).reshape(-1)
+      if w.size != K:
+        raise ValueError(f'len(weights) is {w.size}, the table has {K} levels')
+      cum = state.levels_cum(w)
+    return lanes, eps, cum, int(key) & 0xFFFFFFFFFFFFFFFF
+
+  def _enqueue_levels(self):
+    """crafter_set_levels with the table the batch keeps (None: clear)."""
+    t = self._levels
+    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    with torch.cuda.device(self.device):
+      if t is None:
+        self._check(self._lib.crafter_set_levels(self._handle, None, None, None, 0, 0, self._stream()))
+      else:
+        self._check(self._lib.crafter_set_levels(self._handle, p(t['lanes']), p(t['episodes']), p(t['cum']), int(t['lanes'].numel()),
+                                                 t['key'], self._stream()))
+
+  def set_levels(self, seeds, episodes=None, weights=None, key=0):
+    """Sets the batch's LEVEL TABLE: K levels (seeds[j], episodes[j]), each the episode a fresh crafter.Env(seed=seeds[j]) shows
+    at its episodes[j]-th reset().  While it is set, every reset -- reset(), the automatic one, from the world pool or inline --
+    that takes an env into its k-th episode (k = info['episode'] of the new episode) plays level
+    j = crafter_amd.levels_pick(lane, k, K, cum, key), a counter-based hash of the env's own seed lane and k: uniform over the
+    table, or with probability weights[j] / sum(weights) (a level of weight 0 is not drawn).  No host round trip per finished
+    env, and the world pool keeps serving.  Each env's seed and episode count keep their values and meaning (its draw lane and
+    its reset count): info['episode'], the terminal row and self.seeds do not change.
+    seeds: a host sequence of K hashables, hashed as the reference hashes its seed, or an int64 / uint64 device tensor [K] of
+    lane bits (the first element of levels() of a batch without a table); 1 <= K <= 65536.  episodes: None (1), an int, a host
+    sequence or an int32 device tensor [K].  weights: None (uniform) or K non-negative numbers, not all zero.  key: 64 bits
+    that select another draw sequence over the same table.  Host values are checked before anything is enqueued (ValueError:
+    wrong lengths, K > 65536, an episode outside 1 .. MAX_EPISODE, negative or all-zero weights); device tensors are not read
+    back -- the kernel takes an episode below 1 as 1.  set_levels(None) clears the table: from each env's next reset on the
+    batch plays the episodes of its own seeds again.
+    Enqueued on the current stream; the batch keeps the table's device tensors.  Episodes in progress play on: the table takes
+    effect at each env's next reset.  With the world pool running the call brings the pool to rest and empties EVERY env's
+    entries (they hold worlds of the table being replaced): each env regenerates its next world inline once, then the pool
+    serves it again -- a call for when the table changes, not for every step.
+    With a table set, reseed() / reset(seeds=, episodes=) choose an env's position in its draw sequence, not its level:
+    held-out evaluation on the same batch clears the table first.  copy_envs / save_state / load_state carry lane and episode
+    count, so a copy plays the levels its source would; a store loaded under another table follows that table."""
+    if not hasattr(self._lib, 'crafter_set_levels'):
+      raise _libmod.CrafterLibError('the loaded library has no crafter_set_levels (an older build): level sets are not available')
+    if seeds is None:
+      if episodes is not None or weights is not None:
+        raise ValueError('set_levels(None) clears the table: episodes / weights need seeds')
+      self._levels = None
+      self._enqueue_levels()
+      return
+    lanes, eps, cum, key = self._check_level_set(seeds, episodes, weights, key)
+    for t in (lanes, eps):
+      if torch.is_tensor(t) and t.device != self.device:
+        raise ValueError(f'level tensor on {t.device}, batch on {self.device}')
+    with torch.cuda.device(self.device):
+      if torch.is_tensor(lanes):
+        lanes = lanes.contiguous().view(torch.int64).clone()
+      else:
+        lanes = torch.from_numpy(lanes.view(np.int64)).to(self.device)
+      K = int(lanes.numel())
+      if eps is None:
+        eps = torch.ones(K, dtype=torch.int32, device=self.device)
+      else:
+        eps = eps.contiguous().clone() if torch.is_tensor(eps) else torch.from_numpy(eps).to(self.device)
+      cum_t = None if cum is None else torch.from_numpy(cum.view(np.int32)).to(self.device)   # (the 32 bits of each uint32)
+    self._levels = {'lanes': lanes, 'episodes': eps, 'cum': cum_t, 'key': key, 'cum_host': cum}
+    self._enqueue_levels()
+
+  def level_ids(self, mask=None, out=None):
+    """int32 [N] on the device: the index of the level-table entry of each env's episode in progress -- levels_pick(lane,
+    info['episode']) under the table in force --, -1 in every row while no table is set.  Exact for an episode that began while
+    this table was set (one begun under an earlier table, or before a reseed(), reads what the present table and record say).
+    The exact use: after a step(), the ids of the rows with done != 0 are the levels of the episodes that just began; a
+    level-replay loop keeps its own [N] tensor of them.  Read-only, no wait for the world pool.  mask: rows with a zero byte
+    are left untouched.  out: a contiguous int32 device tensor [N] to write into."""
+    if not hasattr(self._lib, 'crafter_level_ids'):
+      raise _libmod.CrafterLibError('the loaded library has no crafter_level_ids (an older build): level sets are not available')
+    if out is None:
+      out = torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.int32 and
+              tuple(out.shape) == (self.num_envs,) and out.is_contiguous()):
+      raise ValueError(f'out must be a contiguous torch.int32 tensor of shape ({self.num_envs},) on {self.device}')
+    mask, mptr = self._mask(mask, check_len=True)
+    with torch.cuda.device(self.device):
+      self._check(self._lib.crafter_level_ids(self._handle, mptr, C.c_void_p(out.data_ptr()), self._stream()))
+    self._keep = mask
+    return out
 
   def step(self, actions, info=True, out=None, final=False):
     """Env.step() (env.py:83-118) for all envs.  actions: int tensor [N] on the device.

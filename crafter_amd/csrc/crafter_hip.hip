@@ -142,29 +142,30 @@ crafter_frame_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, uint8_t* __restr
 // per step -- measured 10.8 M vs 12.8 M env-steps/s; the spills of the inlined loop only hurt the
 // rare fallback path.
 __device__ __forceinline__ void gen_one(uint8_t* smem, int env, int episode, uint32_t seq, const Config& cfg,
-                                                  const TablePtrs& tb, const StatePtrs& st) {
+                                                  const TablePtrs& tb, const StatePtrs& st, const LevelTable* levels) {
   WaveGfx950<kResetThreads> w;
-  gen_body(w, smem, env, episode, seq, cfg, tb, st);
+  gen_body(w, smem, env, episode, seq, cfg, tb, st, levels);
 }
 
 __device__ __forceinline__ int reset_one(uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb,
-                                                   const StatePtrs& st, uint8_t* obs, int gen_parity) {
+                                                   const StatePtrs& st, uint8_t* obs, int gen_parity, const LevelTable* levels) {
   WaveGfx950<kResetThreads> w;
-  return reset_body(w, smem, env, cfg, tb, st, obs, gen_parity);
+  return reset_body(w, smem, env, cfg, tb, st, obs, gen_parity, levels);
 }
 
 // Regenerates the envs queued by the step kernel (auto-reset without a ready pooled world): a small
 // grid walks the queue of this step's parity and clears the other parity's counter for the next step.
+// levels (here and in the other kernels that seed a world): the handle's level table, null before the first crafter_set_levels.
 __global__ void __launch_bounds__(kRequeueThreads, 5)
 crafter_requeue_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity, int gen_parity,
-                             uint8_t* __restrict__ obs) {
+                             uint8_t* __restrict__ obs, const LevelTable* __restrict__ levels) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int32_t* q = st.reset_q + (size_t)parity * (cfg.num_envs + 4);
   int count = q[0];
   if (blockIdx.x == 0 && threadIdx.x == 0) st.reset_q[(size_t)(1 - parity) * (cfg.num_envs + 4)] = 0;
   for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
     WaveGfx950<kRequeueThreads> w;
-    reset_body(w, smem, q[4 + k], cfg, tb, st, obs, gen_parity);
+    reset_body(w, smem, q[4 + k], cfg, tb, st, obs, gen_parity, levels);
     __syncthreads();
   }
 }
@@ -174,7 +175,7 @@ crafter_requeue_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity,
 // env: terminated, the terminal state's symbolic pair and frame, then Env.reset from the pool or inline (final_reset_body).
 __global__ void __launch_bounds__(kRequeueThreads, 2)
 crafter_requeue_final_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity, int gen_parity, uint32_t safe_seq,
-                             uint8_t* __restrict__ obs, int32_t* __restrict__ next_step, FinalOut fo) {
+                             uint8_t* __restrict__ obs, int32_t* __restrict__ next_step, FinalOut fo, const LevelTable* __restrict__ levels) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int32_t* q = st.reset_q + (size_t)parity * (cfg.num_envs + 4);
   int count = q[0];
@@ -183,7 +184,7 @@ crafter_requeue_final_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity,
   for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
     WaveGfx950<kRequeueThreads> w;
     int env = q[4 + k];
-    if (env >= 0 && env < cfg.num_envs) final_reset_body(w, smem, env, cfg, tb, st, obs, gen_parity, safe_seq, next_step, fo);
+    if (env >= 0 && env < cfg.num_envs) final_reset_body(w, smem, env, cfg, tb, st, obs, gen_parity, safe_seq, next_step, fo, levels);
     __syncthreads();
   }
 }
@@ -193,11 +194,11 @@ crafter_requeue_final_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity,
 // stream order) -- that world may be needed a few dozen steps from now, earlier than any batch could deliver it.
 __global__ void __launch_bounds__(kResetThreads)
 crafter_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask,
-                     int gen_parity, uint8_t* __restrict__ obs) {
+                     int gen_parity, uint8_t* __restrict__ obs, const LevelTable* __restrict__ levels) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   int env = (int)blockIdx.x;
   if (mask && !mask[env]) return;
-  int episode = reset_one(smem, env, cfg, tb, st, obs, -1);
+  int episode = reset_one(smem, env, cfg, tb, st, obs, -1, levels);
   if (gen_parity < 0) return;
   using WR = WaveGfx950<kResetThreads>;
   if (threadIdx.x == 0 && WR::agent_load(st.gen_latest + env) < episode + 1) WR::agent_store(st.gen_latest + env, (int32_t)(episode + 1));
@@ -210,7 +211,7 @@ crafter_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __re
   int32_t pend = WR::agent_load(&next->pending);
   bool have = gen_done_already<WR>(cfg, st, env, episode + 1), busy = pend != 0 && pend != episode + 1;
   __syncthreads();
-  if (!have && !busy) gen_one(smem, env, episode + 1, 1u, cfg, tb, st);
+  if (!have && !busy) gen_one(smem, env, episode + 1, 1u, cfg, tb, st, levels);
   // ... and asks the pool for the one after it right away (it is due two episodes from now; waiting for the first
   // auto-reset to ask would leave a short second episode without its successor)
   WaveGfx950<kResetThreads> w;
@@ -221,7 +222,7 @@ crafter_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __re
 // (env_kernels.hpp gen_seed_body / gen_classify_body / gen_resolve_body).  GEO as for the step kernel.
 template <int GEO>
 __global__ void __launch_bounds__(kGenSeedThreads)
-crafter_gen_seed_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parity, int prio) {
+crafter_gen_seed_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parity, int prio, const LevelTable* __restrict__ levels) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   WaveGfx950<kGenSeedThreads>::set_priority(prio);   // (pool_schedule: one wave per world, a chain -- see there)
   const Config cfg = GEO ? with_default_geometry(cfg_in) : cfg_in;
@@ -230,7 +231,7 @@ crafter_gen_seed_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parity, i
   if (count > gen_q_capacity(cfg)) count = gen_q_capacity(cfg);
   WaveGfx950<kGenSeedThreads> w;
   for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
-    gen_seed_body(w, smem, q[4 + 2 * k], q[4 + 2 * k + 1], cfg, tb, st);
+    gen_seed_body(w, smem, q[4 + 2 * k], q[4 + 2 * k + 1], cfg, tb, st, levels);
     __syncthreads();
   }
 }
@@ -374,6 +375,20 @@ __global__ void __launch_bounds__(kReseedThreads)
 crafter_reseed_kernel(Config cfg, StatePtrs st, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_lane,
                       const int32_t* __restrict__ episode) {
   reseed_body<WaveGfx950<kReseedThreads>>((int)(blockIdx.x * kReseedThreads + threadIdx.x), cfg, st, mask, seed_lane, episode);
+}
+
+// crafter_set_levels (env_levels.hpp): thread i copies table entry i and empties env i's pool entries; thread 0 writes the head.
+__global__ void __launch_bounds__(kLevelThreads)
+crafter_set_levels_kernel(Config cfg, StatePtrs st, LevelTable* __restrict__ table, const uint64_t* __restrict__ seed_lane,
+                          const int32_t* __restrict__ episode, const uint32_t* __restrict__ cum, int n, uint64_t key) {
+  set_levels_body<WaveGfx950<kLevelThreads>>((int)(blockIdx.x * kLevelThreads + threadIdx.x), cfg, st, table, seed_lane, episode, cum, n, key);
+}
+
+// crafter_level_ids: one thread per env, read-only.
+__global__ void __launch_bounds__(kLevelThreads)
+crafter_level_ids_kernel(Config cfg, StatePtrs st, const LevelTable* __restrict__ table, const uint8_t* __restrict__ mask,
+                         int32_t* __restrict__ ids) {
+  level_ids_body((int)(blockIdx.x * kLevelThreads + threadIdx.x), cfg, st, table, mask, ids);
 }
 
 // Builds the renderer's static block once per table upload (one workgroup).
@@ -544,6 +559,8 @@ struct crafter_handle {
   int32_t* copy_mark = nullptr;
   int32_t* copy_verdict = nullptr;
   int32_t copy_stamp = 0;
+  LevelTable* levels = nullptr;        // crafter_set_levels: the level table (env_levels.hpp), allocated once at full capacity by the first call;
+                                       // every kernel that seeds a world takes it as a launch argument (null: no table yet)
   int32_t* subset_actions = nullptr;   // crafter_step_envs: [N] the call's actions scattered to their envs' rows (step_body reads actions[env])
   // optional per-kernel timing (HIP events on the launch stream)
   bool timing = false;
@@ -565,7 +582,7 @@ static int hip_fail(crafter_handle* h, const char* what, hipError_t e) {
 // The three kernels of generation batch `seq` over request segment `seg`, for the plan's GEO
 template <int GEO>
 static void launch_generation(crafter_handle* h, hipStream_t side, dim3 gs, dim3 gc, int seg, uint32_t seq, int prio) {
-  hipLaunchKernelGGL(crafter_gen_seed_kernel<GEO>, gs, dim3(kGenSeedThreads), kGenSeedLds, side, h->cfg, h->tb, h->st, seg, prio);
+  hipLaunchKernelGGL(crafter_gen_seed_kernel<GEO>, gs, dim3(kGenSeedThreads), kGenSeedLds, side, h->cfg, h->tb, h->st, seg, prio, (const LevelTable*)h->levels);
   hipLaunchKernelGGL(crafter_gen_classify_kernel<GEO>, gc, dim3(kGenClassifyThreads), gen_classify_lds_bytes(h->cfg), side, h->cfg, h->tb, h->st, seg, h->gen_classify_prio);
   hipLaunchKernelGGL(crafter_gen_resolve_kernel<GEO>, gs, dim3(kGenResolveThreads), h->gen_resolve_lds_bytes, side, h->cfg, h->tb,
                      h->st, seg, seq, prio);
@@ -1043,7 +1060,8 @@ int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* st
   if (adopt_stream(h, (hipStream_t)stream)) return 1;
   if (h->pool && !h->pool_failed) pool_wait_all(h, (hipStream_t)stream, "hipStreamWaitEvent(reset)");
   hipLaunchKernelGGL(crafter_reset_kernel, dim3(h->cfg.num_envs), dim3(kResetThreads), h->plan.reset_lds,
-                     (hipStream_t)stream, h->cfg, h->tb, h->st, mask, (h->pool && !h->pool_failed) ? h->gen_parity : -1, obs);
+                     (hipStream_t)stream, h->cfg, h->tb, h->st, mask, (h->pool && !h->pool_failed) ? h->gen_parity : -1, obs,
+                     (const LevelTable*)h->levels);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_reset launch", e);
   return 0;
@@ -1165,6 +1183,54 @@ int crafter_reseed(crafter_handle* h, const uint8_t* mask, const uint64_t* seed_
   return 0;
 }
 
+// Level sets (env_levels.hpp).  The table lives in one handle-owned buffer of full capacity, allocated by the first call, so no
+// reallocation is ever ordered against work in flight; kernels enqueued before that call got a null pointer: no table.  Every
+// pooled world was generated under the table being replaced, so the pool is brought to rest as before crafter_reseed and the
+// kernel empties EVERY env's entries.  With the pool off or failed (the step kernels then never adopt) only the table is written.
+int crafter_set_levels(crafter_handle* h, const uint64_t* seed_lane, const int32_t* episode, const uint32_t* cum, int32_t n_levels,
+                       uint64_t key, void* stream) {
+  if (ready(h, "crafter_set_levels")) return 1;
+  if (n_levels < 0 || n_levels > kMaxLevels) return fail(h, "crafter_set_levels: n_levels outside 0 .. " + std::to_string(kMaxLevels));
+  if (n_levels > 0 && (!seed_lane || !episode)) return fail(h, "crafter_set_levels: null seed_lane / episode");
+  bool fresh = false;
+  if (!h->levels) {
+    if (n_levels == 0) return 0;   // no table was ever set: nothing to clear
+    hipError_t ea = hipMalloc((void**)&h->levels, sizeof(LevelTable));
+    if (ea != hipSuccess) return hip_fail(h, "crafter_set_levels: hipMalloc", ea);
+    h->owned.push_back(h->levels);
+    fresh = true;
+  }
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  if (fresh) {   // "no table" until the kernel below has run: the batch pool_quiesce launches (ordered behind this point of the
+                 // stream, ev_main) already takes the pointer
+    hipError_t em = hipMemsetAsync(h->levels, 0, offsetof(LevelTable, lane), (hipStream_t)stream);
+    if (em != hipSuccess) return hip_fail(h, "crafter_set_levels: hipMemsetAsync", em);
+  }
+  pool_quiesce(h, (hipStream_t)stream);
+  StatePtrs st = h->st;
+  if (!h->pool || h->pool_failed) {
+    st.pool_hdr = nullptr;
+    st.gen_latest = nullptr;
+  }
+  const int threads = n_levels > h->cfg.num_envs ? n_levels : h->cfg.num_envs;
+  hipLaunchKernelGGL(crafter_set_levels_kernel, dim3((unsigned)((threads + kLevelThreads - 1) / kLevelThreads)), dim3(kLevelThreads), 0,
+                     (hipStream_t)stream, h->cfg, st, h->levels, seed_lane, episode, n_levels > 0 ? cum : nullptr, (int)n_levels, key);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_set_levels launch", e);
+  return 0;
+}
+
+int crafter_level_ids(crafter_handle* h, const uint8_t* mask, int32_t* ids, void* stream) {
+  if (ready(h, "crafter_level_ids")) return 1;
+  if (!ids) return fail(h, "crafter_level_ids: null ids");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;   // (reads the records and the table only: no wait for the pool beyond that)
+  hipLaunchKernelGGL(crafter_level_ids_kernel, dim3((unsigned)((h->cfg.num_envs + kLevelThreads - 1) / kLevelThreads)), dim3(kLevelThreads), 0,
+                     (hipStream_t)stream, h->cfg, h->st, (const LevelTable*)h->levels, mask, ids);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_level_ids launch", e);
+  return 0;
+}
+
 static int requeue_grid(const crafter_handle* h, const StepCtl& ctl) {
   // With the world pool running the queue is all but always empty (0 of 68,684 resets in the benchmark): a handful of
   // workgroups finds that out faster than 256 (each needs a slot next to the resident generation workgroups).  Without
@@ -1181,11 +1247,11 @@ static void launch_requeue(crafter_handle* h, const StepCtl& ctl, uint8_t* obs, 
     const int grid = h->cfg.num_envs < kRequeueGrid ? h->cfg.num_envs : kRequeueGrid;
     const int lds = h->plan.render_lds > h->plan.reset_lds ? h->plan.render_lds : h->plan.reset_lds;
     CRAFTER_LAUNCH(crafter_requeue_final_kernel, dim3(grid), dim3(kRequeueThreads), lds, stream, start, stop, h->cfg, h->tb, h->st, ctl.parity,
-                   pool_parity, ctl.safe_seq, obs, ctl.next_step, *fin);
+                   pool_parity, ctl.safe_seq, obs, ctl.next_step, *fin, (const LevelTable*)h->levels);
     return;
   }
   CRAFTER_LAUNCH(crafter_requeue_reset_kernel, dim3(requeue_grid(h, ctl)), dim3(kRequeueThreads), h->plan.reset_lds, stream, start, stop,
-                        h->cfg, h->tb, h->st, ctl.parity, ctl.gen_parity, obs);
+                        h->cfg, h->tb, h->st, ctl.parity, ctl.gen_parity, obs, (const LevelTable*)h->levels);
 }
 
 static int need_noise_raw(crafter_handle* h, const char* who) {
@@ -1495,7 +1561,7 @@ int crafter_step_n(crafter_handle* h, int32_t steps, const int32_t* actions, uin
     const bool batch_follows = pooled && requeue && !h->timing && h->fold_main_event && h->steps_since_gen + T >= h->gen_period;
     if (requeue)
       launch_requeue_rollout(requeue_grid(h, ctl), (size_t)h->plan.render_lds, (hipStream_t)stream, ev[2], batch_follows ? h->ev_main : ev[3], h->cfg, h->tb,
-                             h->st, a, o, r, d, ctl, ra);
+                             h->st, a, o, r, d, ctl, ra, h->levels);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(h, "crafter_step_n (auto-reset) launch", e);
     keep_timing_events(h, ev);

@@ -48,14 +48,15 @@ crafter_rollout_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_t*
 // average for that much to come free -- to find its queue empty (profiles/r5_rollout_profile.json: min 4.4 us).
 __global__ void __launch_bounds__(kRequeueThreads, 4)
 crafter_requeue_rollout_kernel(Config cfg, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ actions, uint8_t* __restrict__ obs,
-                               float* __restrict__ reward, uint8_t* __restrict__ done, StepCtl ctl, RolloutArgs ra) {
+                               float* __restrict__ reward, uint8_t* __restrict__ done, StepCtl ctl, RolloutArgs ra,
+                               const LevelTable* __restrict__ levels) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int32_t* q = st.reset_q + (size_t)ctl.parity * (cfg.num_envs + 4);
   int count = q[0];
   if (blockIdx.x == 0 && threadIdx.x == 0) st.reset_q[(size_t)(1 - ctl.parity) * (cfg.num_envs + 4)] = 0;
   for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
     WaveGfx950<kRequeueThreads> w;
-    requeue_rollout_body(w, smem, q[4 + k], cfg, tb, st, actions, obs, reward, done, ctl, ra.T, ra.obs_stride, ra.stalled_at);
+    requeue_rollout_body(w, smem, q[4 + k], cfg, tb, st, actions, obs, reward, done, ctl, ra.T, ra.obs_stride, ra.stalled_at, levels);
     __syncthreads();
   }
 }
@@ -78,9 +79,9 @@ void launch_rollout(int instance, int num_envs, size_t lds, hipStream_t stream, 
 
 void launch_requeue_rollout(int grid, size_t lds, hipStream_t stream, hipEvent_t start, hipEvent_t stop, const Config& cfg,
                             const TablePtrs& tb, const StatePtrs& st, const int32_t* actions, uint8_t* obs, float* reward,
-                            uint8_t* done, const StepCtl& ctl, const RolloutArgs& ra) {
+                            uint8_t* done, const StepCtl& ctl, const RolloutArgs& ra, const LevelTable* levels) {
   CRAFTER_LAUNCH(crafter_requeue_rollout_kernel, dim3(grid), dim3(kRequeueThreads), lds, stream, start, stop, cfg, tb, st, actions, obs,
-                 reward, done, ctl, ra);
+                 reward, done, ctl, ra, levels);
 }
 
 hipError_t rollout_allow_lds(int bytes) {

@@ -39,7 +39,7 @@ void launch_rollout(int instance, int num_envs, size_t lds, hipStream_t stream, 
                     const StepCtl& ctl, const RolloutArgs& ra);
 void launch_requeue_rollout(int grid, size_t lds, hipStream_t stream, hipEvent_t start, hipEvent_t stop, const Config& cfg,
                             const TablePtrs& tb, const StatePtrs& st, const int32_t* actions, uint8_t* obs, float* reward,
-                            uint8_t* done, const StepCtl& ctl, const RolloutArgs& ra);
+                            uint8_t* done, const StepCtl& ctl, const RolloutArgs& ra, const LevelTable* levels);   // levels: env_levels.hpp, null: none
 // large worlds (LaunchPlan::opt_in_lds): lets the generic instances take `bytes` of dynamic LDS
 hipError_t rollout_allow_lds(int bytes);
 

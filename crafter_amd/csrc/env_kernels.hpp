@@ -998,7 +998,7 @@ __device__ __forceinline__ bool emit_frame_cells(Env<W, S>& e, const StatePtrs& 
 
 template <class W, class S = uint16_t>
 __device__ __forceinline__ int reset_body(W& w, uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb, const StatePtrs& st,
-                                 uint8_t* obs, int gen_parity);
+                                 uint8_t* obs, int gen_parity, const LevelTable* levels = nullptr);
 
 // LDS of the frame kernel: record | MT state | second MT state | frame record | night pixel buffer | renderer region
 struct FrameLayout {
@@ -1359,10 +1359,11 @@ __device__ __forceinline__ void rollout_body(W& w, uint8_t* smem, int env, const
 }
 
 // Returns the episode the env is now in.  S: element type of the slot map in THIS kernel's LDS (2 bytes in general, 1 for
-// the default geometry's frame kernel, whose workgroups have the compact layout's room).
+// the default geometry's frame kernel, whose workgroups have the compact layout's room).  levels: the handle's level table
+// (env_levels.hpp; null: none) -- here and in every body below that seeds a world.
 template <class W, class S>
 __device__ __forceinline__ int reset_body(W& w, uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb,
-                                 const StatePtrs& st, uint8_t* obs, int gen_parity) {
+                                 const StatePtrs& st, uint8_t* obs, int gen_parity, const LevelTable* levels) {
   LdsLayout L = sizeof(S) == 2 ? big_reset_layout(cfg) : lds_layout(cfg, (int)sizeof(S));   // (= lds_layout for LDS-resident maps)
   w.scratch = (uint32_t*)(smem + L.scratch);
   Env<W, S> e(w, cfg, tb, smem + L.rules);
@@ -1375,6 +1376,7 @@ __device__ __forceinline__ int reset_body(W& w, uint8_t* smem, int env, const Co
   if (cfg.render_obs != 0 && obs != nullptr) r.preload();   // completes under the barriers below
   load_env(e, st, env, 0);
   WorldGen<W, S> wg(e, smem + L.wg);
+  wg.levels = levels;
   wg.reset_env(prof);
   e.recount_space();
   share_registers(e);
@@ -1396,13 +1398,14 @@ __device__ __forceinline__ int reset_body(W& w, uint8_t* smem, int env, const Co
 template <class W>
 __device__ __forceinline__ void requeue_rollout_body(W& w, uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb,
                                             const StatePtrs& st, const int32_t* actions, uint8_t* obs, float* reward, uint8_t* done,
-                                            const StepCtl& ctl, int T, size_t obs_stride, const int32_t* stalled_at) {
+                                            const StepCtl& ctl, int T, size_t obs_stride, const int32_t* stalled_at,
+                                            const LevelTable* levels = nullptr) {
   StatePtrs sq = st;
   sq.reset_q = nullptr;   // an env that stops again is not queued: it is regenerated right here
   size_t n = (size_t)cfg.num_envs;
   int t = stalled_at[env];
   for (;;) {
-    reset_body<W>(w, smem, env, cfg, tb, st, obs ? obs + (size_t)t * obs_stride : nullptr, ctl.gen_parity);
+    reset_body<W>(w, smem, env, cfg, tb, st, obs ? obs + (size_t)t * obs_stride : nullptr, ctl.gen_parity, levels);
     w.sync();
     bool stopped = false;
     for (t = t + 1; t < T; t++) {
@@ -1422,7 +1425,7 @@ __device__ __forceinline__ void requeue_rollout_body(W& w, uint8_t* smem, int en
 // launch stream may be stepping concurrently): reads only the immutable seed lane.
 template <class W>
 __device__ __forceinline__ void gen_body(W& w, uint8_t* smem, int env, int episode, uint32_t seq, const Config& cfg,
-                                const TablePtrs& tb, const StatePtrs& st) {
+                                const TablePtrs& tb, const StatePtrs& st, const LevelTable* levels = nullptr) {
   LdsLayout L = big_reset_layout(cfg);
   w.scratch = (uint32_t*)(smem + L.scratch);
   if (!gen_wanted<W>(st, env, episode)) return;   // superseded by newer requests of the same env
@@ -1452,6 +1455,7 @@ __device__ __forceinline__ void gen_body(W& w, uint8_t* smem, int env, int episo
   }
   w.sync();
   WorldGen<W> wg(e, smem + L.wg);
+  wg.levels = levels;
   wg.reset_env(nullptr);
   share_registers(e);
   uint4* gob = (uint4*)(st.pool_objs + slot * cfg.max_objects);
@@ -1512,7 +1516,7 @@ static __device__ unsigned long long g_gen_probe[32];
 
 template <class W>
 __device__ __forceinline__ void gen_seed_body(W& w, uint8_t* smem, int env, int episode, const Config& cfg, const TablePtrs& tb,
-                                     const StatePtrs& st) {
+                                     const StatePtrs& st, const LevelTable* levels = nullptr) {
   if (!gen_wanted<W>(st, env, episode) || gen_done_already<W>(cfg, st, env, episode)) return;   // superseded by a newer request of the same env / a duplicate
   Env<W> e(w, cfg, tb);
   e.mt = (uint32_t*)smem;
@@ -1520,7 +1524,7 @@ __device__ __forceinline__ void gen_seed_body(W& w, uint8_t* smem, int env, int 
   e.g_objmap = nullptr;
   w.scratch = (uint32_t*)(smem + kGenSeedLds - 16);
   WorldGen<W> wg(e, smem + align16(4 * MT_N));
-  uint32_t wseed = world_seed(st.rec[env].seed_lane, (uint64_t)episode);   // env.py:74
+  uint32_t wseed = level_seed(levels, st.rec[env].seed_lane, episode);   // env.py:74
   GEN_T0
   if (w.wave0()) wg.init_mt(wseed);
   e.mt_pos = MT_N;
@@ -1826,7 +1830,8 @@ __device__ __forceinline__ void adopt_reset_body(W& w, uint8_t* smem, int env, c
 
 template <class W>
 __device__ __forceinline__ void final_reset_body(W& w, uint8_t* smem, int env, const Config& cfg, const TablePtrs& tb, const StatePtrs& st,
-                                        uint8_t* obs, int gen_parity, uint32_t safe_seq, int32_t* next_step, const FinalOut& fo) {
+                                        uint8_t* obs, int gen_parity, uint32_t safe_seq, int32_t* next_step, const FinalOut& fo,
+                                        const LevelTable* levels = nullptr) {
   if (w.leader()) fo.terminated[env] = st.rec[env].dead != 0 ? 1 : 0;
   if ((fo.local || fo.stats) && w.wave0()) {
     if (lds_layout(cfg).maps_in_lds)
@@ -1845,7 +1850,7 @@ __device__ __forceinline__ void final_reset_body(W& w, uint8_t* smem, int env, c
     if (next_step && w.leader()) next_step[env] = 1;   // (the new episode's first step: what step_body leaves behind an adoption)
   } else {
     if (st.pool_stats && gen_parity >= 0 && w.leader()) w.global_add(st.pool_stats + 1, 1);
-    reset_body<W>(w, smem, env, cfg, tb, st, obs, gen_parity);
+    reset_body<W>(w, smem, env, cfg, tb, st, obs, gen_parity, levels);
   }
 }
 

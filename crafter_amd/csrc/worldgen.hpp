@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "env_core.hpp"
+#include "env_levels.hpp"
 #include "simplex.hpp"
 
 namespace crafter {
@@ -108,6 +109,7 @@ struct WorldGen {
   uint8_t* ridx;     // LDS [256] shuffle indices
   SimplexLds* tab;   // LDS: noise3's gradient and extra-vertex tables
   uint32_t* mtb;     // LDS [624] the MT19937 state AFTER e.mt (random access to >= 624 future words)
+  const LevelTable* levels = nullptr;   // the handle's level table (env_levels.hpp), null: none -- set by the caller before reset_env
 
   __device__ __forceinline__ WorldGen(Env<W, S>& env, uint8_t* lds) : e(env) {
     perm = lds;
@@ -654,7 +656,7 @@ struct WorldGen {
     int cells = c.W * c.H;
     int nch = c.nchunk_x * c.nchunk_y;
     int episode = rec->episode + 1;
-    uint32_t wseed = world_seed(rec->seed_lane, (uint64_t)episode);
+    uint32_t wseed = level_seed(levels, rec->seed_lane, episode);   // env.py:74, of the table's entry where one is set
     e.w.sync();
     e.begin_episode(episode);
     // World.reset engine.py:33-39

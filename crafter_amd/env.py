@@ -196,6 +196,12 @@ class Env(BaseClass):
     local, stats = self._batch.symbolic()
     return local[0].cpu().numpy(), stats[0].cpu().numpy()
 
+  def set_levels(self, seeds, episodes=None, weights=None, key=0):
+    """BatchedEnv.set_levels for this env: its coming reset()s draw their level from the table (None: clear).
+    The table belongs to this object's native handle: a deepcopy or pickle carries seed and episode count, not the table -- set
+    it on the copy."""
+    return self._batch.set_levels(seeds, episodes, weights, key)
+
   def legal_actions(self):
     """BatchedEnv.legal_actions() for this env: bool [n_actions], True where the action passes its guards in the current state."""
     return self._batch.legal_actions()[0].cpu().numpy().astype(bool)

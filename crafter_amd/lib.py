@@ -16,6 +16,7 @@ EXPORTS = [
     'crafter_exchange_wait', 'crafter_exchange_error',
     'crafter_copy_envs', 'crafter_save_envs', 'crafter_load_envs',
     'crafter_symbolic', 'crafter_step_final', 'crafter_reseed', 'crafter_legal_actions', 'crafter_step_envs',
+    'crafter_set_levels', 'crafter_level_ids',
 ]
 
 
@@ -61,7 +62,7 @@ def load(path=None):
   if os.environ.get('CRAFTER_HIP_LIB'):   # an A/B build of an older ABI (tools/ab_make.sh): everything but the newer entry points works
     missing = [n for n in missing if n != 'crafter_extend_daylight' and not n.startswith(('crafter_exchange', 'crafter_step_exchange'))
                and n not in ('crafter_copy_envs', 'crafter_save_envs', 'crafter_load_envs', 'crafter_symbolic', 'crafter_step_final', 'crafter_reseed',
-                             'crafter_legal_actions', 'crafter_step_envs')]
+                             'crafter_legal_actions', 'crafter_step_envs', 'crafter_set_levels', 'crafter_level_ids')]
   if missing:
     raise CrafterLibError(f'{path} lacks symbols {missing}')
   vp, i32 = C.c_void_p, C.c_int32
@@ -119,6 +120,9 @@ def load(path=None):
     lib.crafter_legal_actions.argtypes = [vp, vp, vp, vp]
   if hasattr(lib, 'crafter_step_envs'):
     lib.crafter_step_envs.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+  if hasattr(lib, 'crafter_set_levels'):
+    lib.crafter_set_levels.argtypes = [vp, vp, vp, vp, i32, C.c_uint64, vp]
+    lib.crafter_level_ids.argtypes = [vp, vp, vp, vp]
   sizes = (i32 * 6)()
   lib.crafter_struct_sizes(sizes)
   abi.check_sizes(list(sizes))

@@ -1,7 +1,8 @@
 """``python -m crafter_amd.run_random`` -- the reference's ``crafter/run_random.py`` (lines 10-44) on the
 MI355X path: same flags, same prints (reset time, material counts, step time / FPS, episode length).
 ``--envs N`` (not in the reference) runs N environments at once through BatchedEnv; ``--legal`` (not in the reference either)
-samples uniformly among the actions the legal-action mask allows instead of among all of them."""
+samples uniformly among the actions the legal-action mask allows instead of among all of them; ``--levels K`` (not in the
+reference) draws every episode from a level table of seeds 0 .. K-1 (BatchedEnv.set_levels)."""
 import argparse
 import copy
 import time
@@ -26,6 +27,7 @@ def main(argv=None):
   parser.add_argument('--episodes', type=int, default=1)
   parser.add_argument('--envs', type=int, default=1)
   parser.add_argument('--legal', action='store_true', help='sample uniformly among the legal actions (BatchedEnv.legal_actions)')
+  parser.add_argument('--levels', type=int, default=0, help='draw every episode from a level table of seeds 0 .. K-1 (set_levels)')
   args = parser.parse_args(argv)
 
   import torch
@@ -45,6 +47,8 @@ def main(argv=None):
     env = Env(area=tuple(args.area), length=args.length, seed=args.seed, rules=rules)
     if args.record:   # run_random.py:24: crafter.Recorder(env, args.record) -> stats.jsonl
       env = EnvStatsRecorder(env, args.record)
+    if args.levels:
+      env.set_levels(list(range(args.levels)))
     generator = legal_generator('cpu') if args.legal else None
     for _ in range(args.episodes):
       start = time.time()
@@ -70,6 +74,8 @@ def main(argv=None):
 
   seed = 0 if args.seed is None else args.seed
   env = BatchedEnv(args.envs, area=tuple(args.area), length=args.length, seed=seed, rules=rules, auto_reset=True)
+  if args.levels:
+    env.set_levels(list(range(args.levels)))
   if args.record:
     env = BatchedStatsRecorder(env, args.record)
   generator = legal_generator(env.device) if args.legal else None

@@ -67,6 +67,63 @@ def seed_lanes(seeds):
   return np.array([hash(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
 
 
+MAX_LEVELS = 65536   # capacity of a handle's level table (include/crafter_hip.h crafter_set_levels)
+
+
+def _u64(values):
+  """Anything that holds 64 lane bits (uint64, int64 bit patterns, Python ints of either sign) -> uint64 array."""
+  a = np.asarray(values)
+  if a.dtype == np.uint64:
+    return a
+  if a.dtype.kind == 'i':
+    return a.astype(np.int64).view(np.uint64)
+  if a.dtype.kind == 'u':
+    return a.astype(np.uint64)
+  flat = [int(v) & 0xFFFFFFFFFFFFFFFF for v in np.asarray(values, dtype=object).reshape(-1)]
+  return np.array(flat, dtype=np.uint64).reshape(np.shape(values))
+
+
+def levels_pick(lanes, k, K, cum=None, key=0):
+  """The numpy mirror of the device's `pick` (include/crafter_hip.h crafter_set_levels): the index of the level-table entry an
+  env of draw lane `lanes` plays in its k-th episode, under a table of K entries, cumulative weights `cum` (uint32 [K], None:
+  uniform) and `key`.  lanes (uint64, or int64 / Python ints carrying the 64 bits) and k (ints >= 0) broadcast against each other
+  -> int32 array of that shape.  Exact: the device computes the same integers."""
+  K = int(K)
+  if not 1 <= K <= MAX_LEVELS:
+    raise ValueError(f'K must lie in 1 .. {MAX_LEVELS}')
+  lanes, k = np.broadcast_arrays(_u64(lanes), np.asarray(k, dtype=np.int64).astype(np.uint64))
+  with np.errstate(over='ignore'):
+    z = lanes + np.uint64(0x9E3779B97F4A7C15) * k + np.uint64(int(key) & 0xFFFFFFFFFFFFFFFF)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    u = z >> np.uint64(32)
+    if cum is None:
+      return ((u * np.uint64(K)) >> np.uint64(32)).astype(np.int32)
+  cum = np.asarray(cum)
+  if cum.shape != (K,):
+    raise ValueError(f'cum must have shape ({K},)')
+  # first j with cum[j] > u; cum[K - 1] counts as 2^32 whatever it holds
+  return np.minimum(np.searchsorted(cum[:K - 1].astype(np.uint64), u, side='right'), K - 1).astype(np.int32)
+
+
+def levels_cum(weights):
+  """K weights (non-negative, not all zero) -> cum uint32 [K], cum[j] = min(floor(2^32 * sum(w[:j + 1]) / sum(w)), 2^32 - 1),
+  in exact rational arithmetic."""
+  from fractions import Fraction
+  w = np.asarray(weights).reshape(-1)
+  if w.size == 0 or w.dtype.kind not in 'iuf' or not np.all(np.isfinite(w.astype(np.float64))):
+    raise ValueError('weights must be finite numbers')
+  if (w < 0).any() or not (w > 0).any():
+    raise ValueError('weights must be non-negative and not all zero')
+  vals = [int(v) for v in w] if w.dtype.kind in 'iu' else [Fraction(float(v)) for v in w]
+  total, acc, out = sum(vals), 0, np.zeros(w.size, np.uint32)
+  for j, v in enumerate(vals):
+    acc += v
+    out[j] = min(int(Fraction(acc * 2 ** 32, 1) / total) if not isinstance(acc, int) else (acc << 32) // total, 2 ** 32 - 1)
+  return out
+
+
 def rec_view(rec_bytes):
   """uint8 [N, sizeof(EnvRec)] -> structured array [N]."""
   a = np.ascontiguousarray(rec_bytes)

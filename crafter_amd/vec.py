@@ -130,6 +130,11 @@ class VecEnvView:
       full_seeds[i], full_eps[i], mask[i] = s, e, 1
     return b.reseed(full_seeds, full_eps, mask)
 
+  def set_levels(self, seeds, episodes=None, weights=None, key=0):
+    """BatchedEnv.set_levels: the level table every env's coming resets draw from (None: clear).  Also reachable as
+    ``env_method('set_levels', ...)``: the table belongs to the whole batch, `indices` is ignored."""
+    return self._batch.set_levels(seeds, episodes, weights, key)
+
   def render(self, size=None, mode='rgb_array'):
     return self._batch.render(size).cpu().numpy()
 
@@ -154,10 +159,13 @@ class VecEnvView:
 
   def env_method(self, method_name, *args, indices=None, **kwargs):
     """``env_method('action_masks', indices=...)`` -> the list of rows SB3-contrib's ``get_action_masks`` stacks; there are
-    no per-env Python objects to call anything else on."""
+    no per-env Python objects to call anything else on, except ``env_method('set_levels', ...)``, which sets the batch's table."""
     if method_name == 'action_masks' and not args and not kwargs:
       masks = self.action_masks()
       return [masks[i] for i in self._indices(indices)]
+    if method_name == 'set_levels':
+      result = self.set_levels(*args, **kwargs)
+      return [result for _ in self._indices(indices)]
     raise AttributeError('the batched env has no per-env Python objects to call')
 
   def env_is_wrapped(self, wrapper_class, indices=None):

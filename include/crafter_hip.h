@@ -312,6 +312,46 @@ int crafter_step_envs(crafter_handle* h, const int32_t* idx, int32_t n, const in
  * Additive under ABI revision 7: a binding looks it up by name. */
 int crafter_reseed(crafter_handle* h, const uint8_t* mask, const uint64_t* seed_lane, const int32_t* episode, void* stream);
 
+/* Level sets (no reference counterpart: Procgen's num_levels protocol, level replay, a curriculum -- training on a fixed set of K
+ * levels under auto-reset without a host round trip per finished env).  A handle may hold a LEVEL TABLE: n_levels entries
+ * (seed_lane[j], episode[j] >= 1), 1 <= n_levels <= 65536, optional cumulative weights cum[j] and a 64-bit key.  While a table is
+ * set, the reset that takes an env into its k-th episode (k = rec.episode + 1, counted as always: crafter_reset, the automatic
+ * reset, a world from the pool or one regenerated inline) generates the world of table entry j = pick(rec.seed_lane, k): its seed is
+ * world_seed(seed_lane[j], episode[j]) in place of world_seed(rec.seed_lane, k), and nothing else changes.  rec.seed_lane and
+ * rec.episode keep their values and meaning -- the env's draw lane and its reset count (info['episode'], the terminal row) -- and
+ * the episode played is, bit for bit, the one a fresh crafter.Env(seed) shows at its episode[j]-th reset().
+ * pick, all arithmetic mod 2^64:
+ *   z = seed_lane + 0x9E3779B97F4A7C15 * (uint64)k + key
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31);  u = z >> 32
+ *   cum == NULL (uniform):  j = (u * n_levels) >> 32
+ *   weighted:               j = first index with cum[j] > u   (cum non-decreasing; cum[n_levels - 1] counts as 2^32 whatever
+ *                           it holds; a level of weight 0 -- cum[j] == cum[j - 1], or cum[0] == 0 -- is not drawn)
+ * A host turns weights w into cum[j] = min(floor(2^32 * sum(w[:j + 1]) / sum(w)), 2^32 - 1).  (Under that clamp one value of u in
+ * 2^32, u = 2^32 - 1, falls to the LAST entry whatever its weight.)
+ * crafter_set_levels: all pointers are DEVICE pointers -- seed_lane uint64 [n_levels], episode int32 [n_levels] (a value below 1 is
+ * taken as 1; a caller keeps them <= 2^31 - 3), cum uint32 [n_levels] or NULL.  The call only enqueues: a kernel copies the table
+ * into a buffer the handle owns (allocated once, at the capacity of 65536 entries), so the caller's arrays are free again once
+ * the stream has passed the call.  n_levels == 0 clears the table: from each env's next reset on every world is
+ * world_seed(rec.seed_lane, k) again; a handle that never sets a table behaves exactly as one of a library without these calls.
+ * Errors (crafter_last_error): n_levels outside 0 .. 65536; NULL seed_lane or episode with n_levels > 0.
+ * Episodes in progress are not disturbed: a new table takes effect at each env's next reset.  The world pool's entries all hold
+ * worlds of the table being replaced: the pool is brought to rest as before crafter_reseed and the same kernel empties EVERY
+ * env's two entries and sets gen_latest[env] = rec.episode (no record is edited); each env then regenerates its next world inline
+ * once and the pool takes over.  With the pool off, failed or absent only the table is written.
+ * Copies (crafter_copy_envs / _save_envs / _load_envs) carry lane and k, so a copy plays the levels its source would, and a store
+ * loaded under another table follows that table.  crafter_reseed, with a table set, chooses an env's POSITION in its draw
+ * sequence, not its level: held-out evaluation on the same handle clears the table first.
+ * crafter_level_ids: ids int32 [num_envs] (device), one thread per env, read-only, no wait for the pool:
+ *   ids[env] = pick(rec.seed_lane, rec.episode) under the table in force;  -1 in every row when no table is set;
+ * rows with a zero mask byte (mask uint8 [num_envs] or NULL: all) are untouched.  That is the level of the env's episode in
+ * progress IF THAT EPISODE BEGAN WHILE THIS TABLE WAS SET (an episode begun under an earlier table, or before a crafter_reseed,
+ * reads what the present table and record say, not what it plays).  The exact use: after a step, the ids of the rows with
+ * done != 0 are the levels of the episodes that just began.
+ * Additive under ABI revision 7: a binding looks them up by name. */
+int crafter_set_levels(crafter_handle* h, const uint64_t* seed_lane, const int32_t* episode,
+                       const uint32_t* cum, int32_t n_levels, uint64_t key, void* stream);
+int crafter_level_ids(crafter_handle* h, const uint8_t* mask, int32_t* ids, void* stream);
+
 /* Measurement aid (no reference counterpart): when enabled, crafter_step attaches HIP start / stop events to
  * its two kernels (hipExtLaunchKernelGGL: the kernels' own execution time on the launch stream, what a
  * profiler reports).  crafter_get_timing waits for the recorded events, returns the SUM of step-kernel and
