@@ -7,6 +7,7 @@ from .batched import BatchedEnv, CrafterDeviceError  # noqa: F401
 from .env import Env  # noqa: F401
 from .lib import CrafterLibError  # noqa: F401
 from .state import levels_pick  # noqa: F401
+from .worlds import WorldBank  # noqa: F401
 from .recorder import BatchedEpisodeRecorder, BatchedStatsRecorder, EnvStatsRecorder  # noqa: F401
 from .vec import VecEnvView  # noqa: F401
 

@@ -22,6 +22,7 @@ MAX_USES = 4
 T_NONE, T_PLAYER, T_COW, T_ZOMBIE, T_SKELETON, T_ARROW, T_PLANT = range(7)
 A_NOOP, A_MOVE, A_DO, A_SLEEP, A_PLACE, A_MAKE = range(6)
 ST_OBJ_OVERFLOW, ST_BAD_ACTION, ST_STEP_OVERFLOW, ST_CHUNK_OVERFLOW, ST_POOL_MISMATCH, ST_PIPE_STALL, ST_BAD_COPY = 1, 2, 4, 8, 16, 32, 64
+STATUS_BAD_WORLD = 128   # CRAFTER_ST_BAD_WORLD (include/crafter_hip.h, beside crafter_reset_worlds)
 STATUS_NAMES = {
     ST_OBJ_OVERFLOW: 'object table overflow (raise max_objects)',
     ST_BAD_ACTION: 'action index out of range',
@@ -31,6 +32,13 @@ STATUS_NAMES = {
     ST_PIPE_STALL: 'a bounded in-kernel wait ran out (reserved)',
     ST_BAD_COPY: 'ST_BAD_COPY: copy_envs / load_state / step_envs refused its indices (out of range, duplicate or overlapping destination); nothing was copied or stepped',
 }
+
+# STATUS_NAMES mirrors the enum of crafter_hip_types.h name by name; a bit declared beside its entry point in crafter_hip.h
+# joins it here, and this is the table check_errors() reads
+ALL_STATUS_NAMES = dict(STATUS_NAMES)
+ALL_STATUS_NAMES[STATUS_BAD_WORLD] = (
+    'ST_BAD_WORLD: reset(worlds=...) met a world it had to repair (a material id, an object record or a facing out of range; '
+    'the record was skipped / the value replaced) or a world id outside the bank (that env was left as it was)')
 
 # texture slots of TablePtrs.tex_tile (crafter_hip_types.h CRAFTER_TEX_*)
 TEX_MATERIAL0 = 0

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import abi, lib as _libmod, state, tables
+from . import abi, lib as _libmod, state, tables, worlds as _worlds
 
 _TORCH_DTYPE = {np.uint8: torch.uint8, np.uint16: torch.int16, np.uint32: torch.int32, np.int32: torch.int32, np.float32: torch.float32}
 
@@ -308,20 +308,71 @@ class BatchedEnv:
                     RuntimeWarning, stacklevel=3)
 
   # ------------------------------------------------------------------ Env API
-  def reset(self, mask=None, seeds=None, episodes=None):
+  def reset(self, mask=None, seeds=None, episodes=None, worlds=None, world_ids=None):
     """Env.reset() (env.py:70-81) for all envs, or those with a non-zero mask byte.  Returns obs.
     seeds / episodes: reseed(seeds, episodes, mask) first, in the same call -- the named envs start episode `episodes` (1 by
     default) of `seeds`, the level a fresh crafter.Env(seed=...) shows at that reset().  episodes without seeds: the rows keep
-    their seeds ("restart at episode k")."""
+    their seeds ("restart at episode k").
+    worlds: a crafter_amd.WorldBank -- the named envs reset into AUTHORED worlds instead of generated ones: env i into world
+    world_ids[i] (a host sequence or an int32 device tensor [num_envs]; None: i % len(worlds)).  Everything but the world is
+    Env.reset unchanged -- the episode counter advances, the stream is RandomState(world seed) of that episode from its first
+    word, counters and achievements are cleared -- and the authored world lasts this one episode: the next reset, automatic or
+    not, generates episode k + 1 of the env's seed.  Host ids are checked here (ValueError); a device id outside the bank leaves
+    its env as it was and sets ST_BAD_WORLD (check_errors).  The slot table grows first if the bank's longest world would fill
+    three quarters of it (_grow_objects).  No host round trip: with auto_reset=False, `step(); reset(mask=done, worlds=bank,
+    world_ids=ids)` keeps every env in authored worlds."""
+    if world_ids is not None and worlds is None:
+      raise ValueError('world_ids without worlds')
+    if worlds is not None:
+      if not hasattr(self._lib, 'crafter_reset_worlds'):
+        raise _libmod.CrafterLibError('the loaded library has no crafter_reset_worlds (an older build): authored worlds are not available')
+      if tuple(worlds.area) != (int(self.cfg.W), int(self.cfg.H)):
+        raise ValueError(f'the bank holds {worlds.area[0]} x {worlds.area[1]} worlds, the batch {self.cfg.W} x {self.cfg.H}')
+      if worlds.inv is not None and worlds.inv.shape[1] != len(self.item_names):
+        raise ValueError('the bank was made for rules with another number of items')
+      ids = None
+      if torch.is_tensor(world_ids) and world_ids.is_cuda:
+        if world_ids.dtype != torch.int32 or tuple(world_ids.shape) != (self.num_envs,) or world_ids.device != self.device:
+          raise ValueError(f'world_ids on the device must be an int32 tensor of shape [{self.num_envs}] on {self.device}')
+        ids = world_ids.contiguous()
+      elif world_ids is not None:
+        a = np.asarray(world_ids.cpu() if torch.is_tensor(world_ids) else world_ids).reshape(-1)
+        if a.size != self.num_envs or (a.size and not np.issubdtype(a.dtype, np.integer)):
+          raise ValueError(f'world_ids must be {self.num_envs} integers')
+        if a.size and (a.min() < 0 or a.max() >= len(worlds)):
+          raise ValueError(f'world_ids must lie in 0 .. {len(worlds) - 1}')
+        ids = torch.from_numpy(a.astype(np.int32)).to(self.device)
+      if self.grow_objects and 4 * worlds.max_objects > 3 * self.cfg.max_objects:   # (check_errors' own rule, ahead of the reset)
+        self._grow_objects(max(2 * self.cfg.max_objects, 2 * worlds.max_objects))
     if seeds is not None or episodes is not None:
       kept = self._reseed(seeds, episodes, mask)
     else:
       kept = None
-    mask, mptr = self._mask(mask)
+    mask, mptr = self._mask(mask, check_len=worlds is not None)
     with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_reset(self._handle, mptr, C.c_void_p(self.obs.data_ptr()), self._stream()))
+      if worlds is None:
+        self._check(self._lib.crafter_reset(self._handle, mptr, C.c_void_p(self.obs.data_ptr()), self._stream()))
+      else:
+        t = worlds.device_tensors(self.device)
+        self._check(self._lib.crafter_reset_worlds(
+            self._handle, mptr, None if ids is None else C.c_void_p(ids.data_ptr()), C.c_void_p(t['mat'].data_ptr()),
+            C.c_void_p(t['objs'].data_ptr()), C.c_void_p(t['nobj'].data_ptr()), None if t['inv'] is None else C.c_void_p(t['inv'].data_ptr()),
+            len(worlds), int(worlds.objs.shape[1]), C.c_void_p(self.obs.data_ptr()), self._stream()))
+        kept = (kept, worlds, t, ids)
     self._keep = mask if kept is None else (mask, kept)
     return self.obs
+
+  def export_worlds(self, idx=None):
+    """The current worlds of envs idx (all by default) as host arrays, in exactly the form WorldBank accepts --
+    dict(mat [K, W, H], objects: per env the live objects in slot order, the player first, as (type, x, y, health, (fx, fy),
+    aux), inventory [K, n_items]) -- so that `WorldBank(env, **edit(env.export_worlds()))` authors a world by editing a
+    generated one.  Synchronises."""
+    i, _ = self._index(np.arange(self.num_envs) if idx is None else idx, self.num_envs, 'idx')
+    rows = i.long()
+    rec = state.rec_view(self.state['rec'][rows].cpu().numpy())
+    objs = state.objs_view(self.state['objs'][rows].cpu().numpy())
+    mat = self.state['mat'][rows].cpu().numpy().reshape(-1, self.cfg.W, self.cfg.H)
+    return _worlds.worlds_of(mat, objs, rec, len(self.item_names))
 
   # ------------------------------------------------------------------ levels (include/crafter_hip.h crafter_reseed)
   MAX_EPISODE = 2 ** 31 - 3   # the world pool asks for episode + 2
@@ -970,7 +1021,7 @@ class BatchedEnv:
     if bad.numel():
       i = int(bad[0])
       bits = int(status[i]) & 0xFFFFFFFF
-      names = [v for k, v in abi.STATUS_NAMES.items() if bits & k]
+      names = [v for k, v in abi.ALL_STATUS_NAMES.items() if bits & k]
       raise CrafterDeviceError(f'env {i}: {", ".join(names) or hex(bits)} ({bad.numel()} envs affected)')
 
   def snapshot(self, i):

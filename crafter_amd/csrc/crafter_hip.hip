@@ -22,6 +22,7 @@
 #include "env_copy.hpp"
 #include "env_kernels.hpp"
 #include "env_levels.hpp"
+#include "env_worlds.hpp"
 #include "launch_plan.hpp"
 #include "legal.hpp"
 #include "symbolic.hpp"
@@ -189,16 +190,12 @@ crafter_requeue_final_kernel(Config cfg, TablePtrs tb, StatePtrs st, int parity,
   }
 }
 
-// Env.reset.  With the world pool on (gen_parity >= 0) the workgroup goes on to generate the NEXT episode's world into
-// the env's pool entry, stamped with batch sequence 1 (trusted from the start: this kernel precedes every later step in
+// What a reset kernel's workgroup does to its env's pool entries once the env stands in `episode` (crafter_reset_kernel,
+// crafter_reset_worlds_kernel): with the world pool on (gen_parity >= 0) it goes on to generate the NEXT episode's world into
+// the env's pool entry, stamped with batch sequence 1 (trusted from the start: the kernel precedes every later step in
 // stream order) -- that world may be needed a few dozen steps from now, earlier than any batch could deliver it.
-__global__ void __launch_bounds__(kResetThreads)
-crafter_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask,
-                     int gen_parity, uint8_t* __restrict__ obs, const LevelTable* __restrict__ levels) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  int env = (int)blockIdx.x;
-  if (mask && !mask[env]) return;
-  int episode = reset_one(smem, env, cfg, tb, st, obs, -1, levels);
+__device__ __forceinline__ void reset_pool_tail(uint8_t* smem, int env, int episode, int gen_parity, const Config& cfg, const TablePtrs& tb,
+                                                const StatePtrs& st, const LevelTable* levels) {
   if (gen_parity < 0) return;
   using WR = WaveGfx950<kResetThreads>;
   if (threadIdx.x == 0 && WR::agent_load(st.gen_latest + env) < episode + 1) WR::agent_store(st.gen_latest + env, (int32_t)(episode + 1));
@@ -216,6 +213,35 @@ crafter_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __re
   // auto-reset to ask would leave a short second episode without its successor)
   WaveGfx950<kResetThreads> w;
   request_generation(w, cfg, st, gen_parity, env, episode + 2);
+}
+
+// Env.reset.  Then reset_pool_tail.
+__global__ void __launch_bounds__(kResetThreads)
+crafter_reset_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask,
+                     int gen_parity, uint8_t* __restrict__ obs, const LevelTable* __restrict__ levels) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  int env = (int)blockIdx.x;
+  if (mask && !mask[env]) return;
+  int episode = reset_one(smem, env, cfg, tb, st, obs, -1, levels);
+  reset_pool_tail(smem, env, episode, gen_parity, cfg, tb, st, levels);
+}
+
+// Env.reset into an authored world of the bank (env_worlds.hpp), one workgroup per env with crafter_reset_kernel's threads and
+// LDS; then the same tail: the episode after an authored one is an ordinary generated one.  An env whose world id names no
+// world is left alone (its pool entries too).
+__global__ void __launch_bounds__(kResetThreads)
+crafter_reset_worlds_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, WorldBank bank,
+                            int gen_parity, uint8_t* __restrict__ obs, const LevelTable* __restrict__ levels) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  int env = (int)blockIdx.x;
+  if (mask && !mask[env]) return;
+  int episode;
+  {
+    WaveGfx950<kResetThreads> w;
+    episode = reset_world_body(w, smem, env, cfg, tb, st, bank, obs, levels);
+  }
+  if (episode < 0) return;
+  reset_pool_tail(smem, env, episode, gen_parity, cfg, tb, st, levels);
 }
 
 // World pool generation (side streams): three kernels per batch, each walking the batch's segment of the request queue
@@ -665,7 +691,7 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
     if constexpr (GEO != 1) big.push_back((const void*)crafter_step_kernel<LM, GEO, RUL>);
     CRAFTER_STEP_INSTANCES(CRAFTER_X)
 #undef CRAFTER_X
-    for (const void* f : {(const void*)crafter_reset_kernel, (const void*)crafter_gen_resolve_kernel<0>,
+    for (const void* f : {(const void*)crafter_reset_kernel, (const void*)crafter_reset_worlds_kernel, (const void*)crafter_gen_resolve_kernel<0>,
                           (const void*)crafter_requeue_reset_kernel, (const void*)crafter_requeue_final_kernel,
                           (const void*)crafter_render_kernel})
       big.push_back(f);
@@ -1064,6 +1090,34 @@ int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* st
                      (const LevelTable*)h->levels);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(h, "crafter_reset launch", e);
+  return 0;
+}
+
+// Env.reset into authored worlds: crafter_reset with another world source (env_worlds.hpp).  The kernel ends on the reset
+// kernel's own tail (reset_pool_tail), so the launch stream is ordered behind the pool exactly as there.
+int crafter_reset_worlds(crafter_handle* h, const uint8_t* mask, const int32_t* world_id, const uint8_t* bank_mat, const crafter_obj* bank_objs,
+                         const int32_t* bank_nobj, const int32_t* bank_inv, int32_t n_worlds, int32_t bank_max_objects, uint8_t* obs,
+                         void* stream) {
+  if (ready(h, "crafter_reset_worlds")) return 1;
+  if (!bank_mat || !bank_objs || !bank_nobj) return fail(h, "crafter_reset_worlds: bank_mat, bank_objs and bank_nobj must not be NULL");
+  if (n_worlds < 1) return fail(h, "crafter_reset_worlds: n_worlds must be at least 1");
+  if (bank_max_objects < 0) return fail(h, "crafter_reset_worlds: bank_max_objects must not be negative");
+  if (((uintptr_t)bank_objs & 15u) != 0) return fail(h, "crafter_reset_worlds: bank_objs must be 16-byte aligned");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  if (h->pool && !h->pool_failed) pool_wait_all(h, (hipStream_t)stream, "hipStreamWaitEvent(reset_worlds)");
+  WorldBank bank;
+  bank.world_id = world_id;
+  bank.mat = bank_mat;
+  bank.objs = bank_objs;
+  bank.nobj = bank_nobj;
+  bank.inv = bank_inv;
+  bank.n_worlds = n_worlds;
+  bank.max_objects = bank_max_objects;
+  hipLaunchKernelGGL(crafter_reset_worlds_kernel, dim3(h->cfg.num_envs), dim3(kResetThreads), h->plan.reset_lds, (hipStream_t)stream,
+                     h->cfg, h->tb, h->st, mask, bank, (h->pool && !h->pool_failed) ? h->gen_parity : -1, obs,
+                     (const LevelTable*)h->levels);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(h, "crafter_reset_worlds launch", e);
   return 0;
 }
 

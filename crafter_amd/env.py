@@ -12,7 +12,7 @@ import collections
 import numpy as np
 import torch
 
-from . import batched, tables
+from . import batched, tables, worlds as _worlds
 
 try:  # gym is optional in the reference too (env.py:11-22)
   import gym
@@ -137,17 +137,23 @@ class Env(BaseClass):
   def action_names(self):
     return self._batch.action_names
 
-  def reset(self, seed=None, episode=None):
+  def reset(self, seed=None, episode=None, world=None):
     """Env.reset() (env.py:70-81).  seed (Gymnasium's reset(seed=...)): the env becomes crafter.Env(seed=seed) at its
     episode-th reset (default 1) -- that level, and the episodes that follow it; _seed and _episode say so, and a deepcopy
-    or pickle taken afterwards carries the new seed.  episode alone restarts the current seed at that episode."""
+    or pickle taken afterwards carries the new seed.  episode alone restarts the current seed at that episode.
+    world: dict(mat [W, H], objects, inventory=None) -- one world in the form of crafter_amd.WorldBank (what export_world()
+    returns): this episode plays in it instead of a generated world; the next reset() generates again."""
+    bank = None
+    if world is not None:   # (raises ValueError before anything changes)
+      inv = world.get('inventory')
+      bank = _worlds.WorldBank(self._batch, np.asarray(world['mat'])[None], [world.get('objects', [])], None if inv is None else [inv])
     if seed is None and episode is None:
       self._episode += 1
       self._step = 0
-      obs = self._batch.reset()
+      obs = self._batch.reset(worlds=bank)
     else:
       episode = 1 if episode is None else int(episode)
-      obs = self._batch.reset(seeds=None if seed is None else [seed], episodes=[episode])   # (raises before anything changes)
+      obs = self._batch.reset(seeds=None if seed is None else [seed], episodes=[episode], worlds=bank)   # (raises before anything changes)
       if seed is not None:
         self._seed = seed
       self._episode = episode
@@ -186,6 +192,11 @@ class Env(BaseClass):
     if not self._reward:
       reward = 0.0
     return obs, reward, done, info
+
+  def export_world(self):
+    """The world as it stands, in the form reset(world=...) takes: dict(mat [W, H], objects, inventory)."""
+    w = self._batch.export_worlds([0])
+    return dict(mat=w['mat'][0], objects=w['objects'][0], inventory=w['inventory'][0])
 
   def render(self, size=None):
     size = None if size is None else tuple(int(v) for v in (size if hasattr(size, '__len__') else (size, size)))

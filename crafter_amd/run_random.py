@@ -2,7 +2,8 @@
 MI355X path: same flags, same prints (reset time, material counts, step time / FPS, episode length).
 ``--envs N`` (not in the reference) runs N environments at once through BatchedEnv; ``--legal`` (not in the reference either)
 samples uniformly among the actions the legal-action mask allows instead of among all of them; ``--levels K`` (not in the
-reference) draws every episode from a level table of seeds 0 .. K-1 (BatchedEnv.set_levels)."""
+reference) draws every episode from a level table of seeds 0 .. K-1 (BatchedEnv.set_levels); ``--worlds FILE.npz`` (not in the
+reference) plays the authored worlds of a bank saved by ``WorldBank.save`` instead of generated ones."""
 import argparse
 import copy
 import time
@@ -28,6 +29,7 @@ def main(argv=None):
   parser.add_argument('--envs', type=int, default=1)
   parser.add_argument('--legal', action='store_true', help='sample uniformly among the legal actions (BatchedEnv.legal_actions)')
   parser.add_argument('--levels', type=int, default=0, help='draw every episode from a level table of seeds 0 .. K-1 (set_levels)')
+  parser.add_argument('--worlds', type=str, default=None, help='play the authored worlds of a bank saved by WorldBank.save (reset(worlds=...))')
   args = parser.parse_args(argv)
 
   import torch
@@ -42,6 +44,38 @@ def main(argv=None):
     generator = torch.Generator(device=device)
     generator.manual_seed(0 if args.seed is None else args.seed)
     return generator
+
+  if args.worlds:   # authored worlds: every episode of every env plays a world of the bank, chosen at random on the device
+    from . import WorldBank
+    bank = WorldBank.load(args.worlds, rules)
+    seed = 0 if args.seed is None else args.seed
+    env = BatchedEnv(args.envs, area=bank.area, length=args.length, seed=seed, rules=rules, auto_reset=False)
+    generator = torch.Generator(device=env.device)
+    generator.manual_seed(seed)
+    pick = lambda: torch.randint(0, len(bank), (args.envs,), generator=generator, device=env.device, dtype=torch.int32)
+    legal = legal_generator(env.device) if args.legal else None
+    start = time.time()
+    env.reset(worlds=bank, world_ids=pick())
+    torch.cuda.synchronize()
+    print(f'Reset time: {1000 * (time.time() - start):.2f}ms for {args.envs} envs into {len(bank)} authored worlds')
+    finished, steps = 0, 0
+    start = time.time()
+    while finished < args.episodes * args.envs:
+      if args.legal:
+        actions = sample_legal(env.legal_actions(), legal)
+      else:
+        actions = torch.from_numpy(random.randint(0, env.num_actions, size=args.envs).astype(np.int32)).to(env.device)
+      _, _, done, _ = env.step(actions, info=False)
+      env.reset(mask=done, worlds=bank, world_ids=pick())   # no host round trip: the mask stays on the device
+      steps += args.envs
+      if steps // args.envs % 64 == 0:
+        finished = int(env.records()['episode'].sum()) - args.envs
+    torch.cuda.synchronize()
+    duration = time.time() - start
+    env.check_errors()
+    print(f'Step time: {1000 * duration / (steps / args.envs):.3f}ms per batched step ({int(steps / duration)} env-steps/s)')
+    print('Episodes finished:', int(env.records()['episode'].sum()) - args.envs)
+    return
 
   if args.envs == 1:
     env = Env(area=tuple(args.area), length=args.length, seed=args.seed, rules=rules)

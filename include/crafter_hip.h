@@ -111,6 +111,49 @@ int32_t crafter_step_instance(const crafter_handle* h);
  * mask: device uint8[num_envs].  obs: device uint8[num_envs][size_h][size_w][3] or NULL. */
 int crafter_reset(crafter_handle* h, const uint8_t* mask, uint8_t* obs, void* stream);
 
+/* Authored worlds: Env.reset (env.py:70-81) with worldgen.generate_world(world, player) replaced by "write this map, add these
+ * objects" -- the env then stands in a world the CALLER designed (additive under revision 7: a binding looks the entry point
+ * up by name).  For every env whose mask byte is non-zero, with j = world_id[env] (world_id == NULL: env % n_worlds):
+ *     world material map[:] = bank_mat[j]                               [W][H], index x * H + y
+ *     for r in bank_objs[j][0 .. bank_nobj[j]), in order:
+ *         r.type == CRAFTER_T_PLAYER (allowed as record 0 only):
+ *             if (r.x, r.y) is not the centre: World.move(player, (r.x, r.y));  player.facing = (r.fx, r.fy)
+ *         else: World.add(Cow | Zombie | Skeleton | Arrow | Plant at (r.x, r.y)) with health = r.health, r.aux as the zombie's
+ *             cooldown / the skeleton's reload / the plant's grown, and for an arrow facing = (r.fx, r.fy)
+ *     player.inventory = bank_inv[j]                                    if given; else the rules' initial inventory
+ * Everything before and after is Env.reset unchanged: the episode counter advances by one, World.reset, RandomState(world
+ * seed) seeded exactly as crafter_reset seeds it (a level table in force included), the player added at the centre first (slot
+ * 1; its chunk is the first chunk key), step 0, hunger / thirst / fatigue / recover and the achievements cleared, the first
+ * frame drawn.  The authored function draws nothing: the episode's stream starts at the first word of RandomState(world seed).
+ * Slots are 2, 3, ... in record order, chunk keys are inserted in the order the calls above touch them, and every derived
+ * table of the row (cell -> slot map, census, nobj) is what those calls leave.  An authored world lasts ONE episode: the next
+ * one is the ordinary generated episode k + 1 of the env's seed.
+ *
+ * The bank is checked on the device, record by record; nothing in it can make a kernel read or write outside a table.  Each of
+ * the following sets the sticky CRAFTER_ST_BAD_WORLD in the env's record, and the reset still completes into a consistent row:
+ *   - a material byte outside 1 .. n_materials is written as rules.mat_grass;
+ *   - a record is skipped if its type is none of the six classes, if its cell lies outside the world or is already
+ *     occupied, or if it is a PLAYER record other than record 0;
+ *   - a facing (player, arrow) that is no unit axis vector is written as (0, 1).  The other classes keep no facing: their
+ *     fx / fy are ignored and stored as (0, 0), as World.add's other callers store them.
+ * A world id outside 0 .. n_worlds - 1 sets the bit and leaves the row (and its pool entries) untouched.  Records beyond the
+ * batch's slot table set CRAFTER_ST_OBJ_OVERFLOW, as every World.add does.  A PLAYER record's health and aux are ignored
+ * (the player's health is the inventory's).
+ *
+ * All pointers are device pointers.  mask: uint8[num_envs] or NULL (all), as for crafter_reset; rows with a zero byte are
+ * neither read nor written.  world_id: int32[num_envs] or NULL.  bank_mat: uint8[n_worlds][W * H].  bank_objs:
+ * crafter_obj[n_worlds][bank_max_objects], 16-byte aligned.  bank_nobj: int32[n_worlds], taken as clamped to
+ * 0 .. bank_max_objects.  bank_inv: int32[n_worlds][rules.n_items] or NULL, each value taken as clamped to 0 .. item_max.
+ * obs as for crafter_reset.  Host-side errors: a NULL bank_mat / bank_objs / bank_nobj, a misaligned bank_objs,
+ * n_worlds < 1, bank_max_objects < 0.  The call only enqueues; the bank must stay alive and unchanged until the work has run.
+ * It is ordered behind the world pool exactly as crafter_reset is, and afterwards each env does to its pool entries exactly
+ * what crafter_reset does (the next episode's world is generated into its entry, the one after is requested).
+ * A bank drawn from by the AUTOMATIC reset inside crafter_step is deliberately not offered. */
+#define CRAFTER_ST_BAD_WORLD 128   /* sticky status bit, beside CRAFTER_ST_* of crafter_hip_types.h */
+int crafter_reset_worlds(crafter_handle* h, const uint8_t* mask, const int32_t* world_id, const uint8_t* bank_mat,
+                         const crafter_obj* bank_objs, const int32_t* bank_nobj, const int32_t* bank_inv, int32_t n_worlds,
+                         int32_t bank_max_objects, uint8_t* obs, void* stream);
+
 /* Replaces Env.step (env.py:83-118) for all envs.
  * actions: device int32[num_envs]; obs as above; reward: device float[num_envs];
  * done: device uint8[num_envs].  With cfg->auto_reset, envs that finished are regenerated
