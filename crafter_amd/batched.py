@@ -737,6 +737,56 @@ class BatchedEnv:
     self._keep = (actions, o, r, d)
     return o, r, d
 
+  def rollout_envs(self, idx, actions, out=None, obs=True):
+    """rollout() for the envs idx names and for no other, with compact outputs (crafter_step_n_envs): the playouts of a tree
+    search or a random-shooting planner over the scratch rows of a large batch, an action repeat of a few envs.  idx: n env
+    indices, 1 <= n <= N, none twice, any order; actions: int32 [T, n] ([n] when T == 1), actions[t, i] for env idx[i] at its
+    step t.  Returns (obs u8[T,n,H,W,3] or None, reward f32[T,n], done u8[T,n]): row i belongs to env idx[i].  For a named env
+    the call is exactly T calls of step_envs() that name it -- auto-reset, pool, terminal row and info['semantic'] included --
+    in one launch per stretch, its state resident in LDS over the stretch; every other row, of the state too, is neither read
+    nor written.  self.obs / self.reward / self.done are NOT updated; the state is.
+    idx is checked as for step_envs(): host indices raise ValueError before anything is enqueued, a device tensor is checked on
+    the device -- a bad list refuses the whole call, no state row and no output byte changes, and check_errors() raises
+    (ST_BAD_COPY).  out = (obs or None, reward, done): tensors of those shapes to write into.  obs=False, or a batch with
+    render=False: no frames.  An empty idx enqueues nothing."""
+    if not hasattr(self._lib, 'crafter_step_n_envs'):
+      raise _libmod.CrafterLibError('the loaded library has no crafter_step_n_envs (an older build): rollout_envs is not available')
+    i, hi = self._index(idx, self.num_envs, 'idx')
+    if hi is not None and len(np.unique(hi)) != len(hi):
+      raise ValueError('idx names an env twice')
+    n = int(i.numel())
+    if n > self.num_envs:
+      raise ValueError(f'idx names {n} envs, the batch has {self.num_envs}')
+    actions = self._actions(actions)
+    if actions.dim() == 1:
+      actions = actions.reshape(1, -1)
+    if actions.dim() != 2 or actions.shape[1] != n or actions.shape[0] < 1:
+      raise ValueError(f'actions must have shape [T, {n}] with T >= 1 (idx names {n} envs)')
+    T = int(actions.shape[0])
+    obs = obs and bool(self.cfg.render_obs)   # render=False: no kernel draws, there is no frame to return
+    shapes = (((T, n) + tuple(self.obs.shape[1:]), torch.uint8), ((T, n), torch.float32), ((T, n), torch.uint8))
+    if out is None:
+      o, r, d = (torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
+      if not obs:
+        o = None
+    else:
+      o, r, d = out   # (as rollout(): an obs tensor given here is written whatever `obs` says)
+      for t, (shape, dt) in zip((o, r, d), shapes):
+        if t is None and shape is shapes[0][0]:
+          continue
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and
+                t.data_ptr() % 16 == 0):
+          raise ValueError(f'out tensor must be a contiguous, 16-byte aligned {dt} device tensor of shape {shape}')
+    if n:
+      if self._unbounded:
+        self._grow_daylight(T)
+      with torch.cuda.device(self.device):
+        self._check(self._lib.crafter_step_n_envs(
+            self._handle, C.c_void_p(i.data_ptr()), n, T, C.c_void_p(actions.data_ptr()), C.c_void_p(o.data_ptr()) if o is not None else None,
+            C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()), self._stream()))
+      self._keep = (i, actions, o, r, d)
+    return o, r, d
+
   @staticmethod
   def _check_out(t, like):
     if not (t.is_cuda and t.dtype == like.dtype and t.shape == like.shape and t.is_contiguous() and t.data_ptr() % 16 == 0):

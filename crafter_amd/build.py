@@ -10,6 +10,7 @@ ROOT = pathlib.Path(__file__).resolve().parent
 SRC = ROOT / 'csrc' / 'crafter_hip.hip'
 SRC_ROLLOUT = ROOT / 'csrc' / 'crafter_rollout.hip'   # crafter_step_n's kernels: one more flag (csrc/crafter_rollout.hpp)
 SRC_SUBSET = ROOT / 'csrc' / 'crafter_subset.hip'     # crafter_step_envs' kernels: the step kernel's flags (csrc/crafter_subset.hpp)
+SRC_ROLLOUT_SUBSET = ROOT / 'csrc' / 'crafter_rollout_subset.hip'   # crafter_step_n_envs' kernels: the rollout unit's flags (csrc/crafter_rollout_subset.hpp)
 OUT = ROOT / '_lib' / 'libcrafter_hip.so'
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared']
 CFLAGS = [f for f in FLAGS if f != '-shared']
@@ -17,7 +18,7 @@ ROLLOUT_FLAGS = ['-mllvm', '-disable-machine-licm']
 
 
 def sources():
-  return ([SRC, SRC_ROLLOUT, SRC_SUBSET] + sorted((ROOT / 'csrc').glob('*.hpp')) + sorted((ROOT / 'csrc').glob('*.inc')) +
+  return ([SRC, SRC_ROLLOUT, SRC_SUBSET, SRC_ROLLOUT_SUBSET] + sorted((ROOT / 'csrc').glob('*.hpp')) + sorted((ROOT / 'csrc').glob('*.inc')) +
           [ROOT.parent / 'include' / 'crafter_hip.h', ROOT.parent / 'include' / 'crafter_hip_types.h'])
 
 
@@ -43,7 +44,8 @@ def build(force=False, verbose=False, out=None, defines=(), root=None):
   target = pathlib.Path(out) if out else OUT
   target.parent.mkdir(exist_ok=True)
   csrc = ROOT / 'csrc' if root is None else pathlib.Path(root) / 'crafter_amd' / 'csrc'
-  units = [(csrc / SRC.name, []), (csrc / SRC_ROLLOUT.name, ROLLOUT_FLAGS), (csrc / SRC_SUBSET.name, [])]
+  units = [(csrc / SRC.name, []), (csrc / SRC_ROLLOUT.name, ROLLOUT_FLAGS), (csrc / SRC_SUBSET.name, []),
+           (csrc / SRC_ROLLOUT_SUBSET.name, ROLLOUT_FLAGS)]
   dflags = [f'-D{d}' for d in defines]
   import tempfile
   from concurrent.futures import ThreadPoolExecutor
@@ -79,7 +81,7 @@ def resource_usage():
   hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
   text = ''
   with tempfile.TemporaryDirectory() as tmp:
-    for src, extra in ((SRC, []), (SRC_ROLLOUT, ROLLOUT_FLAGS), (SRC_SUBSET, [])):
+    for src, extra in ((SRC, []), (SRC_ROLLOUT, ROLLOUT_FLAGS), (SRC_SUBSET, []), (SRC_ROLLOUT_SUBSET, ROLLOUT_FLAGS)):
       cmd = [hipcc] + CFLAGS + extra + ['-Rpass-analysis=kernel-resource-usage', '-c', '-o', str(pathlib.Path(tmp) / 'x.o'), str(src)]
       proc = subprocess.run(cmd, capture_output=True, text=True)
       if proc.returncode != 0:

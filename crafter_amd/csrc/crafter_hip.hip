@@ -17,6 +17,7 @@
 
 #include "../../include/crafter_hip.h"
 #include "crafter_rollout.hpp"
+#include "crafter_rollout_subset.hpp"
 #include "crafter_subset.hpp"
 #include "dispatch_order.hpp"
 #include "env_copy.hpp"
@@ -588,6 +589,7 @@ struct crafter_handle {
   LevelTable* levels = nullptr;        // crafter_set_levels: the level table (env_levels.hpp), allocated once at full capacity by the first call;
                                        // every kernel that seeds a world takes it as a launch argument (null: no table yet)
   int32_t* subset_actions = nullptr;   // crafter_step_envs: [N] the call's actions scattered to their envs' rows (step_body reads actions[env])
+  int32_t* rollout_row_of = nullptr;   // crafter_step_n_envs: [N] the row of the call's compact outputs each named env writes (its place in idx)
   // optional per-kernel timing (HIP events on the launch stream)
   bool timing = false;
   std::vector<hipEvent_t> events;   // triples: before step, between, after reset
@@ -704,6 +706,12 @@ int crafter_create(const crafter_config* cfg, crafter_handle** out) {
     er = subset_allow_lds(h->plan.render_lds);   // ... and crafter_step_envs' in crafter_subset.hip
     if (er != hipSuccess) {
       std::string msg = std::string("crafter_create: hipFuncSetAttribute(subset kernels): ") + hipGetErrorString(er);
+      delete h;
+      return fail(nullptr, msg);
+    }
+    er = rollout_envs_allow_lds(h->plan.render_lds);   // ... and crafter_step_n_envs' in crafter_rollout_subset.hip
+    if (er != hipSuccess) {
+      std::string msg = std::string("crafter_create: hipFuncSetAttribute(subset rollout kernels): ") + hipGetErrorString(er);
       delete h;
       return fail(nullptr, msg);
     }
@@ -1618,6 +1626,81 @@ int crafter_step_n(crafter_handle* h, int32_t steps, const int32_t* actions, uin
                              h->st, a, o, r, d, ctl, ra, h->levels);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(h, "crafter_step_n (auto-reset) launch", e);
+    keep_timing_events(h, ev);
+    if (pooled) pool_schedule(h, (hipStream_t)stream, T, batch_follows, true);
+    pooled = h->pool && !h->pool_failed;
+    done_steps += T;
+  }
+  return 0;
+}
+
+// crafter_step_n for the n envs idx names, and for no other, with compact outputs (crafter_rollout_subset.hpp): the index check
+// once, in front of the first stretch -- its verdict stays valid for the call's later stretches, calls on a handle being
+// serialised --, then crafter_step_n's stretch loop over the subset's kernels.
+int crafter_step_n_envs(crafter_handle* h, const int32_t* idx, int32_t n, int32_t steps, const int32_t* actions, uint8_t* obs, float* reward,
+                        uint8_t* done, void* stream) {
+  if (ready(h, "crafter_step_n_envs")) return 1;
+  if (n < 0 || n > h->cfg.num_envs) return fail(h, "crafter_step_n_envs: n outside 0 .. num_envs");
+  if (n == 0) return 0;
+  if (!idx) return fail(h, "crafter_step_n_envs: null index list");
+  if (!actions || !reward || !done || steps < 1) return fail(h, "crafter_step_n_envs: bad argument");
+  if (adopt_stream(h, (hipStream_t)stream)) return 1;
+  bool pooled = h->pool && !h->pool_failed;
+  if (!h->stalled_at) {
+    hipError_t ea = hipMalloc((void**)&h->stalled_at, (size_t)h->cfg.num_envs * sizeof(int32_t));
+    if (ea != hipSuccess) return hip_fail(h, "crafter_step_n_envs: hipMalloc", ea);
+    h->owned.push_back(h->stalled_at);
+  }
+  if (!h->rollout_row_of) {
+    hipError_t ea = hipMalloc((void**)&h->rollout_row_of, (size_t)h->cfg.num_envs * sizeof(int32_t));
+    if (ea != hipSuccess) return hip_fail(h, "crafter_step_n_envs: row scratch", ea);
+    h->owned.push_back(h->rollout_row_of);
+  }
+  const bool frames = obs != nullptr && h->cfg.render_obs != 0;
+  if (frames && need_noise_raw(h, "crafter_step_n_envs: noise scratch")) return 1;
+  if (h->plan.night_px && frames && need_night_px(h, "crafter_step_n_envs: night frame scratch")) return 1;   // big_layout
+  RolloutEnvsCheck chk;
+  chk.idx = idx; chk.n = n;
+  if (index_check_scratch(h, "crafter_step_n_envs", (hipStream_t)stream, &chk.stamp)) return 1;
+  chk.mark = h->copy_mark; chk.verdict = h->copy_verdict; chk.rec = (EnvRec*)h->st.rec; chk.rows = h->cfg.num_envs;
+  chk.row_of = h->rollout_row_of;
+  const size_t rows = (size_t)n;
+  const size_t obs_stride = rows * (size_t)h->cfg.size_w * h->cfg.size_h * 3;
+  const bool requeue = h->cfg.auto_reset != 0;
+  for (int done_steps = 0; done_steps < steps;) {
+    int left = steps - done_steps;
+    // stretches as crafter_step_n's: up to the pool's next generation batch, kUnpooledStretch steps without the pool
+    int room = pooled ? h->gen_period - h->steps_since_gen : (left < kUnpooledStretch ? left : kUnpooledStretch);
+    int T = left < room ? left : (room > 0 ? room : 1);
+    const int32_t* a = actions + (size_t)done_steps * rows;
+    uint8_t* o = obs ? obs + (size_t)done_steps * obs_stride : nullptr;
+    float* r = reward + (size_t)done_steps * rows;
+    uint8_t* d = done + (size_t)done_steps * rows;
+    StepCtl ctl;
+    ctl.parity = (int)(h->steps++ & 1);
+    ctl.gen_parity = pooled ? h->gen_parity : -1;
+    ctl.safe_seq = h->safe_seq;
+    ctl.next_step = h->next_step;   // an ordered handle: the named envs' entries stay current; the launch follows no order and builds none
+    if (frames) ctl.noise_raw = h->noise_raw;
+    if (h->plan.night_px) ctl.night_px = h->night_px;
+    RolloutEnvsArgs ra;
+    ra.idx = idx; ra.verdict = h->copy_verdict; ra.row_of = h->rollout_row_of; ra.n = n; ra.T = T; ra.stalled_at = h->stalled_at;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (timing_events(h, ev, "crafter_step_n_envs: hipEventCreate (timing mode)")) return 1;
+    // timing mode: the first stretch's step time runs from the check's start to the rollout kernel's end
+    if (done_steps == 0) launch_rollout_envs_check(chk, (hipStream_t)stream, ev[0], nullptr);
+    launch_rollout_envs(h->plan.instance, (size_t)h->plan.rollout_lds, (hipStream_t)stream, done_steps == 0 ? nullptr : ev[0], ev[1], h->cfg, h->tb,
+                        h->st, a, o, r, d, ctl, ra);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(h, "crafter_step_n_envs launch", e);
+    // (a generation batch follows this stretch: its side stream waits for the stretch's last kernel through that kernel's
+    // own stop event, as in crafter_step_n)
+    const bool batch_follows = pooled && requeue && !h->timing && h->fold_main_event && h->steps_since_gen + T >= h->gen_period;
+    if (requeue)
+      launch_requeue_rollout_envs(requeue_grid(h, ctl), (size_t)h->plan.render_lds, (hipStream_t)stream, ev[2], batch_follows ? h->ev_main : ev[3],
+                                  h->cfg, h->tb, h->st, a, o, r, d, ctl, ra, h->levels);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(h, "crafter_step_n_envs (auto-reset) launch", e);
     keep_timing_events(h, ev);
     if (pooled) pool_schedule(h, (hipStream_t)stream, T, batch_follows, true);
     pooled = h->pool && !h->pool_failed;

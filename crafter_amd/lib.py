@@ -16,7 +16,7 @@ EXPORTS = [
     'crafter_exchange_wait', 'crafter_exchange_error',
     'crafter_copy_envs', 'crafter_save_envs', 'crafter_load_envs',
     'crafter_symbolic', 'crafter_step_final', 'crafter_reseed', 'crafter_legal_actions', 'crafter_step_envs',
-    'crafter_set_levels', 'crafter_level_ids', 'crafter_reset_worlds',
+    'crafter_set_levels', 'crafter_level_ids', 'crafter_reset_worlds', 'crafter_step_n_envs',
 ]
 
 
@@ -62,7 +62,8 @@ def load(path=None):
   if os.environ.get('CRAFTER_HIP_LIB'):   # an A/B build of an older ABI (tools/ab_make.sh): everything but the newer entry points works
     missing = [n for n in missing if n != 'crafter_extend_daylight' and not n.startswith(('crafter_exchange', 'crafter_step_exchange'))
                and n not in ('crafter_copy_envs', 'crafter_save_envs', 'crafter_load_envs', 'crafter_symbolic', 'crafter_step_final', 'crafter_reseed',
-                             'crafter_legal_actions', 'crafter_step_envs', 'crafter_set_levels', 'crafter_level_ids', 'crafter_reset_worlds')]
+                             'crafter_legal_actions', 'crafter_step_envs', 'crafter_set_levels', 'crafter_level_ids', 'crafter_reset_worlds',
+                             'crafter_step_n_envs')]
   if missing:
     raise CrafterLibError(f'{path} lacks symbols {missing}')
   vp, i32 = C.c_void_p, C.c_int32
@@ -125,6 +126,8 @@ def load(path=None):
     lib.crafter_level_ids.argtypes = [vp, vp, vp, vp]
   if hasattr(lib, 'crafter_reset_worlds'):
     lib.crafter_reset_worlds.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+  if hasattr(lib, 'crafter_step_n_envs'):
+    lib.crafter_step_n_envs.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
   sizes = (i32 * 6)()
   lib.crafter_struct_sizes(sizes)
   abi.check_sizes(list(sizes))

@@ -335,6 +335,34 @@ int crafter_step_final(crafter_handle* h, const int32_t* actions, uint8_t* obs, 
 int crafter_step_envs(crafter_handle* h, const int32_t* idx, int32_t n, const int32_t* actions,
                       uint8_t* obs, float* reward, uint8_t* done, void* stream);
 
+/* crafter_step_n for a chosen subset of the batch, with COMPACT outputs (no reference counterpart: a Monte-Carlo playout, a
+ * random-shooting planner or an action repeat over the scratch rows of a large batch would otherwise pay `steps` calls of
+ * crafter_step_envs, or roll out every env of the batch).
+ *   idx:     device int32[n], 1 <= n <= num_envs: the envs to roll out.  Every entry in range, no env named twice, any order.
+ *   actions: device int32[steps][n]: actions[t][i] is the action of env idx[i] at its step t.
+ *   reward:  device float[steps][n];  done: device uint8[steps][n];
+ *   obs:     device uint8[steps][n][size_h][size_w][3] or NULL.  Row i of every output belongs to env idx[i].
+ * For every named env the call is exactly `steps` consecutive calls of crafter_step_envs that name it: its state, each step's
+ * obs / reward / done, its terminal row, info['semantic'], the auto-reset from the pool or through the regeneration kernel
+ * behind the launch, its requests to the pool, level tables, crafter_reseed and authored worlds in progress.  Rows of envs
+ * that are not named are neither read nor written, in the bound state or anywhere else.  (As between crafter_step and
+ * crafter_step_n, "its state" is every byte a reader of the state looks at: the FREE records of the slot table behind the
+ * env's nobj keep whatever was last stored there, and the table goes back to global memory once per launch here.)
+ * n == 0 returns 0 and enqueues nothing; idx == NULL, n < 0, n > num_envs, steps < 1 and NULL actions / reward / done are
+ * errors (crafter_last_error).
+ * The index list is checked on the device before any env steps, as for crafter_step_envs: a bad list refuses the WHOLE call
+ * -- no state row and no output byte changes -- and sets CRAFTER_ST_BAD_COPY in the status of the named rows that exist (row 0
+ * if none exists).
+ * One launch of n workgroups covers the steps up to the world pool's next generation batch, or 16 steps when the pool is off,
+ * exactly as crafter_step_n splits its call; each env's state stays in LDS over the steps of a launch.  The call counts as
+ * `steps` steps of the pool's batch period.  It may be mixed freely with crafter_step, crafter_step_envs, crafter_step_final,
+ * crafter_step_n and the copy calls.  On a handle that keeps a dispatch order it follows none and builds none; it keeps the
+ * named envs' entries of the order's input current.  crafter_set_timing attaches its events per launch, as for crafter_step_n.
+ * There is no `final` variant and no exchange variant of this call.
+ * Additive under ABI revision 7: a binding looks it up by name. */
+int crafter_step_n_envs(crafter_handle* h, const int32_t* idx, int32_t n, int32_t steps, const int32_t* actions,
+                        uint8_t* obs, float* reward, uint8_t* done, void* stream);
+
 /* Level selection (no reference counterpart as a call: the reference fixes the seed in Env.__init__, env.py:32, and a world is a
  * pure function of (seed, episode), env.py:74).  For every env whose mask byte is non-zero (mask == NULL: all):
  *   rec.seed_lane = seed_lane[i];  rec.episode = max(episode[i], 1) - 1;
