@@ -7,28 +7,24 @@ import numpy as np
 
 from crafter_amd import abi, state, tables
 from . import build as _build
+from .build import ptr as _ptr
 
-_libs = {}
+_checked = set()
 _STATIC_BLOCKS = {}   # renderer static blocks by content key (HostSimEnv._table_ptrs)
 
 
 def lib(variant=None):
   """variant: None, or (tag, defines) for a differently configured build of the same sources."""
-  if variant not in _libs:
-    path = _build.build() if variant is None else _build.build(tag=variant[0], defines=variant[1])
-    l = C.CDLL(str(path))
+  l = _build.lib('hostsim', variant)
+  if variant not in _checked:
     sizes = (C.c_int32 * 6)()
     l.hostsim_struct_sizes(sizes)
     abi.check_sizes(list(sizes))
     l.hostsim_world_seed.restype = C.c_uint32
     l.hostsim_render_static_bytes.restype = C.c_longlong
     l.hostsim_world_seed.argtypes = [C.c_uint64, C.c_uint64]
-    _libs[variant] = l
-  return _libs[variant]
-
-
-def _ptr(a):
-  return a.ctypes.data_as(C.c_void_p)
+    _checked.add(variant)
+  return l
 
 
 class HostSimEnv:

@@ -3,40 +3,8 @@
 // after reset() -- config, tables, state buffers -- and an action tape; plays the tape and prints one line per env that finished,
 //   t env terminated fnv(final_obs row) fnv(final_local row) fnv(final_stats row) fnv(obs row)
 // which the test compares with the same run through the shared library.
-#include <stdio.h>
-#include <stdlib.h>
-
 #include "final_host.cpp"
-
-namespace {
-
-struct Blob {
-  std::vector<std::vector<uint8_t>> parts;
-  bool read(const char* path) {
-    FILE* f = fopen(path, "rb");
-    if (!f) return false;
-    uint64_t n = 0;
-    while (fread(&n, 8, 1, f) == 1) {
-      std::vector<uint8_t> p((size_t)n);
-      if (n && fread(p.data(), 1, (size_t)n, f) != (size_t)n) {
-        fclose(f);
-        return false;
-      }
-      parts.push_back(std::move(p));
-    }
-    fclose(f);
-    return true;
-  }
-};
-
-uint64_t fnv(const void* p, size_t n) {
-  const uint8_t* b = (const uint8_t*)p;
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
-  return h;
-}
-
-}  // namespace
+#include "blob.hpp"
 
 int main(int argc, char** argv) {
   if (argc != 2) {
@@ -44,26 +12,17 @@ int main(int argc, char** argv) {
     return 2;
   }
   Blob b;
-  constexpr int kTables = (int)(sizeof(TablePtrs) / sizeof(void*)), kState = (int)(sizeof(StatePtrs) / sizeof(void*));
-  if (!b.read(argv[1]) || (int)b.parts.size() != 3 + kTables + kState) {
+  // parts: [steps, pool_mode, split] int32 | Config, tables, state (blob.hpp bind_env) | actions
+  Config cfg;
+  TablePtrs tb;
+  StatePtrs st;
+  if (!b.read(argv[1]) || (int)b.parts.size() != 1 + Blob::kEnvParts + 1 || !b.bind_env(1, cfg, tb, st)) {
     fprintf(stderr, "bad blob\n");
     return 2;
   }
-  // parts: [steps, pool_mode, split] int32 | Config | the tables, in TablePtrs order | the state, in StatePtrs order (empty: null) | actions
   const int32_t* head = (const int32_t*)b.parts[0].data();
   const int T = head[0], pool_mode = head[1], split = head[2];
-  if (b.parts[1].size() != sizeof(Config)) return 2;
-  Config cfg;
-  memcpy(&cfg, b.parts[1].data(), sizeof(Config));
-  void* tp[kTables];
-  for (int i = 0; i < kTables; i++) tp[i] = b.parts[2 + i].empty() ? nullptr : b.parts[2 + i].data();
-  void* sp[kState];
-  for (int i = 0; i < kState; i++) sp[i] = b.parts[2 + kTables + i].empty() ? nullptr : b.parts[2 + kTables + i].data();
-  TablePtrs tb;
-  StatePtrs st;
-  memcpy(&tb, tp, sizeof(tb));
-  memcpy(&st, sp, sizeof(st));
-  const std::vector<uint8_t>& acts = b.parts[2 + kTables + kState];
+  const std::vector<uint8_t>& acts = b.parts[1 + Blob::kEnvParts];
   const size_t n = (size_t)cfg.num_envs;
   if (acts.size() != (size_t)T * n * 4) return 2;
   const size_t frame = (size_t)cfg.size_w * cfg.size_h * 3, nl = 2 * (size_t)cfg.local_gw * cfg.local_gh, ns = (size_t)tb.rules->n_items + 4;
@@ -75,9 +34,8 @@ int main(int argc, char** argv) {
     if (rc < 0) return 3;
     for (size_t i = 0; i < n; i++)
       if (done[i])
-        printf("%d %d %d %016llx %016llx %016llx %016llx\n", t, (int)i, (int)terminated[i], (unsigned long long)fnv(&final_obs[i * frame], frame),
-               (unsigned long long)fnv(&final_local[i * nl], nl), (unsigned long long)fnv(&final_stats[i * ns], ns * 4),
-               (unsigned long long)fnv(&obs[i * frame], frame));
+        printf("%d %d %d %016llx %016llx %016llx %016llx\n", t, (int)i, (int)terminated[i], fnv(&final_obs[i * frame], frame), fnv(&final_local[i * nl], nl),
+               fnv(&final_stats[i * ns], ns * 4), fnv(&obs[i * frame], frame));
   }
   return 0;
 }

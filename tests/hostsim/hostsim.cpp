@@ -5,9 +5,7 @@
 
 #include <vector>
 
-#include "wave_host.hpp"
-#include "../../crafter_amd/csrc/env_kernels.hpp"
-#include "../../crafter_amd/csrc/launch_plan.hpp"
+#include "walks.hpp"
 
 using namespace crafter;
 
@@ -72,37 +70,15 @@ void hostsim_exp_cr(const double* x, double* out, int n) {
 }
 
 // pool_mode: 0 = world pool off, 1 = pool on with generation right after every call (always trusted)
-static void run_generation(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, std::vector<uint8_t>& lds) {
-  int32_t* q = st->gen_q;
-  int count = q ? q[0] : 0;
-  if (count > gen_q_capacity(*cfg)) count = gen_q_capacity(*cfg);
-  for (int k = 0; k < count; k++) {
-    // the product's three-kernel pipeline (seed -> classify -> resolve), each stage in freshly poisoned "LDS"
-    int env = q[4 + 2 * k], episode = q[4 + 2 * k + 1];
-    WaveHost w;
-    memset(lds.data(), 0xCD, lds.size());
-    gen_seed_body(w, lds.data(), env, episode, *cfg, *tb, *st);
-    memset(lds.data(), 0xCD, lds.size());
-    for (int part = 0, parts = gen_classify_parts(*cfg); part < parts; part++) {
-      memset(lds.data(), 0xCD, lds.size());
-      gen_classify_body(w, lds.data(), env, episode, part, parts, *cfg, *tb, *st);
-    }
-    memset(lds.data(), 0xCD, lds.size());
-    gen_resolve_body(w, lds.data(), env, episode, 1u, *cfg, *tb, *st);
-  }
-  if (q) q[0] = 0;
-}
-
 int hostsim_reset(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const uint8_t* mask,
                   int pool_mode, uint8_t* obs) {
-  std::vector<uint8_t> lds(lds_layout(*cfg).total + 64);
+  FakeLds lds = step_lds(*cfg);
   for (int env = 0; env < cfg->num_envs; env++) {
     if (mask && !mask[env]) continue;
-    memset(lds.data(), 0xCD, lds.size());
     WaveHost w;
-    reset_body(w, lds.data(), env, *cfg, *tb, *st, obs, pool_mode ? 0 : -1);
+    reset_body(w, lds.fresh(), env, *cfg, *tb, *st, obs, pool_mode ? 0 : -1);
   }
-  if (pool_mode) run_generation(cfg, tb, st, lds);
+  if (pool_mode) run_generation(*cfg, *tb, *st, lds);
   return 0;
 }
 
@@ -115,63 +91,19 @@ void hostsim_set_noise_ahead(int on) { g_noise_ahead = on; }
 
 int hostsim_step(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const int32_t* actions,
                  uint8_t* obs, float* reward, uint8_t* done, int pool_mode) {
-  std::vector<uint8_t> lds(lds_layout(*cfg).total + frame_layout(*cfg).total + 64);
+  FakeLds lds = split_step_lds(*cfg);
   const LaunchPlan plan = launch_plan(*cfg, is_default_rules(*tb->rules));
-  // (the library splits the default instance only: choose_step; no dispatch order here, and always the early frame -- see below)
-  bool split = lane_layout_ok(*cfg) && is_split(choose_step(plan, cfg->num_envs, cfg->render_obs && obs, false, g_split ? 1 : 0, 0, 1));
-  StepCtl ctl;
-  ctl.parity = 0;
-  ctl.gen_parity = pool_mode ? 0 : -1;
-  ctl.safe_seq = 0xffffffffu;
-  ctl.early_frame = 1;   // (the library: batches larger than the chip holds at once; here always, so that the path is covered)
-  // split step: the frame kernel's scratch (night pixels)
-  static std::vector<uint32_t> night_px;
-  night_px.resize((size_t)cfg->num_envs * frame_night_px_words(*cfg));
-  static std::vector<uint32_t> noise_raw;   // the fused step's noise look-ahead scratch (noise_chain); g_noise_ahead 0: the in-frame pass
-  noise_raw.resize((size_t)cfg->num_envs * kNoiseStates * MT_N);
-  if (g_noise_ahead) ctl.noise_raw = noise_raw.data();
-  bool frames = split && cfg->render_obs && obs;
-  for (int env = 0; env < cfg->num_envs; env++) {
-    memset(lds.data(), 0xCD, lds.size());
-    WaveHost w;
-    StepCtl big = ctl;   // big_layout: census in place, night pixels in global scratch
-    big.night_px = night_px.data();
-    if (split) {
-      step_body<WaveHost, -1, 1, LaneSlots, 1>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
-    } else switch (plan.instance) {   // crafter_step_kernel<LM, GEO, RUL>; here LM -1 for maps in "LDS", and the staged rules where they are
-      case kInstance111:
-      case kInstance110:   // one-byte slot ids for crafter.Env()'s defaults
-        step_body<WaveHost, -1, 0, uint8_t>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
-        break;
-      case kInstance100:
-        step_body<WaveHost, -1, 0, uint16_t>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
-        break;
-      case kInstance021:   // the default rules compiled in
-        step_body<WaveHost, 0, 1, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, big);
-        break;
-      case kInstance000:
-        step_body<WaveHost, 0, 0, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, big);
-        break;
-    }
-  }
-  if (frames) {   // the frame kernel
-    for (int env = 0; env < cfg->num_envs; env++) {
-      memset(lds.data(), 0xCD, lds.size());
-      WaveHost wf;
-      frame_body(wf, lds.data(), env, *cfg, *tb, *st, obs, night_px.data());
-    }
-  }
+  static CtlScratch scratch;
+  // early_frame 1 (the library: batches larger than the chip holds at once; here always, so that the path is covered)
+  const StepCtls c = make_ctls(*cfg, scratch, pool_mode ? 0 : -1, 1, g_noise_ahead != 0);
+  step_batch(plan, step_is_split(*cfg, plan, obs, g_split), c, lds, *cfg, *tb, *st, actions, obs, reward, done);
   if (cfg->auto_reset) {
     // same queue walk as crafter_requeue_reset_kernel
-    int32_t* q = st->reset_q;
-    int count = q ? q[0] : 0;
-    for (int k = 0; k < count; k++) {
-      memset(lds.data(), 0xCD, lds.size());
+    drain_reset_q(*st, [&](int env) {
       WaveHost w;
-      reset_body(w, lds.data(), q[4 + k], *cfg, *tb, *st, obs, ctl.gen_parity);
-    }
-    if (q) q[0] = 0;
-    if (pool_mode) run_generation(cfg, tb, st, lds);
+      reset_body(w, lds.fresh(), env, *cfg, *tb, *st, obs, c.ctl.gen_parity);
+    });
+    if (pool_mode) run_generation(*cfg, *tb, *st, lds);
   }
   return 0;
 }
@@ -180,14 +112,11 @@ int hostsim_step(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, co
 // rollout_body, then the regeneration queue through requeue_rollout_body, then (pool on) the generation batch.
 int hostsim_step_n(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, int steps, const int32_t* actions,
                    uint8_t* obs, float* reward, uint8_t* done, int pool_mode, int stretch) {
-  std::vector<uint8_t> lds(lds_layout(*cfg).total + 64);
+  FakeLds lds = step_lds(*cfg);
   std::vector<int32_t> stalled_at((size_t)cfg->num_envs, -1);
   const LaunchPlan plan = launch_plan(*cfg, is_default_rules(*tb->rules));
-  std::vector<uint32_t> night_px(plan.night_px ? (size_t)cfg->num_envs * frame_night_px_words(*cfg) : 0);   // (big_layout)
-  StepCtl ctl;
-  ctl.parity = 0;
-  ctl.gen_parity = pool_mode ? 0 : -1;
-  ctl.safe_seq = 0xffffffffu;
+  CtlScratch scratch;
+  const StepCtls c = make_ctls(*cfg, scratch, pool_mode ? 0 : -1, 0, false, plan.night_px != 0);
   size_t n = (size_t)cfg->num_envs, obs_stride = n * (size_t)cfg->size_w * cfg->size_h * 3;
   for (int t0 = 0; t0 < steps; t0 += stretch) {
     int T = steps - t0 < stretch ? steps - t0 : stretch;
@@ -196,48 +125,30 @@ int hostsim_step_n(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, 
     float* r = reward + (size_t)t0 * n;
     uint8_t* d = done + (size_t)t0 * n;
     for (int env = 0; env < cfg->num_envs; env++) {
-      memset(lds.data(), 0xCD, lds.size());
       WaveHost w;
-      StepCtl big = ctl;
-      big.night_px = night_px.data();
-      switch (plan.instance) {   // crafter_rollout_kernel<LM, GEO, RUL>, the template arguments as in hostsim_step
-        case kInstance111:
-        case kInstance110:
-          rollout_body<WaveHost, -1, 0, uint8_t>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
-          break;
-        case kInstance100:
-          rollout_body<WaveHost, -1, 0, uint16_t>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
-          break;
-        case kInstance021:
-          rollout_body<WaveHost, 0, 1, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, big, T, obs_stride, stalled_at.data());
-          break;
-        case kInstance000:
-          rollout_body<WaveHost, 0, 0, FarSlot>(w, lds.data(), env, *cfg, *tb, *st, a, o, r, d, big, T, obs_stride, stalled_at.data());
-          break;
-      }
+      uint8_t* l = lds.fresh();
+      with_instance(plan, c, [&](auto inst, const StepCtl& ctl) {   // crafter_rollout_kernel<LM, GEO, RUL>
+        using I = decltype(inst);
+        rollout_body<WaveHost, I::LM, I::RUL, typename I::Slot>(w, l, env, *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
+      });
     }
     if (cfg->auto_reset) {
-      int32_t* q = st->reset_q;
-      int count = q ? q[0] : 0;
-      for (int k = 0; k < count; k++) {
-        memset(lds.data(), 0xCD, lds.size());
+      drain_reset_q(*st, [&](int env) {
         WaveHost w;
-        requeue_rollout_body(w, lds.data(), q[4 + k], *cfg, *tb, *st, a, o, r, d, ctl, T, obs_stride, stalled_at.data());
-      }
-      if (q) q[0] = 0;
-      if (pool_mode) run_generation(cfg, tb, st, lds);
+        requeue_rollout_body(w, lds.fresh(), env, *cfg, *tb, *st, a, o, r, d, c.ctl, T, obs_stride, stalled_at.data());
+      });
+      if (pool_mode) run_generation(*cfg, *tb, *st, lds);
     }
   }
   return 0;
 }
 
 int hostsim_render(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const uint8_t* mask, uint8_t* out) {
-  std::vector<uint8_t> lds(lds_layout(*cfg).total + 64);
+  FakeLds lds = step_lds(*cfg);
   for (int env = 0; env < cfg->num_envs; env++) {
     if (mask && !mask[env]) continue;
-    memset(lds.data(), 0xCD, lds.size());
     WaveHost w;
-    render_body(w, lds.data(), env, *cfg, *tb, *st, out);
+    render_body(w, lds.fresh(), env, *cfg, *tb, *st, out);
   }
   return 0;
 }

@@ -2,28 +2,17 @@
 // (sanitised code is never loaded into Python).  Reads one blob written by tests/hostsim/legal_build.py dump(): Config | Rules |
 // mat | objmap | objs | rec | row mask (empty: none), each part in a buffer of exactly its size, so that a read past an end is
 // a finding.  Prints the mask, one line of 0 / 1 per env ('-' for a row left untouched).
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
 #include "legal_host.cpp"
+#include "blob.hpp"
 
 int main(int argc, char** argv) {
   if (argc != 2) {
     fprintf(stderr, "usage: %s blob\n", argv[0]);
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  std::vector<std::vector<uint8_t>> parts;
-  uint64_t n = 0;
-  while (fread(&n, 8, 1, f) == 1) {
-    std::vector<uint8_t> p((size_t)n);
-    if (n && fread(p.data(), 1, (size_t)n, f) != (size_t)n) return 2;
-    parts.push_back(std::move(p));
-  }
-  fclose(f);
+  Blob b;
+  if (!b.read(argv[1])) return 2;
+  std::vector<std::vector<uint8_t>>& parts = b.parts;
   if (parts.size() != 7 || parts[0].size() != sizeof(Config) || parts[1].size() != sizeof(Rules)) {
     fprintf(stderr, "bad blob\n");
     return 2;

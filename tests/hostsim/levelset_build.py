@@ -1,47 +1,22 @@
-"""TEST INFRASTRUCTURE: builds tests/hostsim/_build/libhostsim_levelset.so (the level-set bodies of csrc/env_levels.hpp and the
-reset / step walks with a level table, levelset_host.cpp) with g++, with the flags of tests/hostsim/build.py."""
+"""TEST INFRASTRUCTURE: the level-set bodies of csrc/env_levels.hpp and the reset / step walks with a level table on the CPU
+(levelset_host.cpp, built by tests/hostsim/build.py)."""
 import ctypes as C
-import pathlib
-import subprocess
 
 import numpy as np
 
 from crafter_amd import state
-from .driver import HostSimEnv, _ptr
-
-HERE = pathlib.Path(__file__).resolve().parent
-OUT = HERE / '_build' / 'libhostsim_levelset.so'
-SRCS = [HERE / 'levelset_host.cpp', HERE / 'wave_host.hpp'] + sorted((HERE.parent.parent / 'crafter_amd' / 'csrc').glob('*.hpp')) + [
-    HERE.parent.parent / 'include' / 'crafter_hip_types.h']   # csrc/types.hpp includes it
-
-_lib = None
-
-
-def build(force=False):
-  newest = max(p.stat().st_mtime for p in SRCS)
-  if not force and OUT.exists() and OUT.stat().st_mtime >= newest:
-    return OUT
-  OUT.parent.mkdir(exist_ok=True)
-  cmd = ['g++', '-std=c++17', '-O2', '-g', '-ffp-contract=off', '-fno-fast-math', '-fPIC', '-shared',
-         '-Wall', '-Wno-unused-variable', '-Wno-unknown-pragmas', '-D__device__=', '-D__host__=',
-         '-D__forceinline__=inline', '-DCRAFTER_LIT_SPRITE_STEPS=96', '-o', str(OUT), str(HERE / 'levelset_host.cpp')]
-  subprocess.run(cmd, check=True)
-  return OUT
+from .driver import HostSimEnv
+from . import build as _build
+from .build import ptr as _p
 
 
 def lib():
-  global _lib
-  if _lib is None:
-    _lib = C.CDLL(str(build()))
-    _lib.hostsim_level_table_bytes.restype = C.c_longlong
-    _lib.hostsim_level_seed.restype = C.c_uint32
-    _lib.hostsim_level_seed.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
-    _lib.hostsim_set_levels.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_uint64]
-  return _lib
-
-
-def _p(a):
-  return None if a is None else a.ctypes.data_as(C.c_void_p)
+  l = _build.lib('levelset')
+  l.hostsim_level_table_bytes.restype = C.c_longlong
+  l.hostsim_level_seed.restype = C.c_uint32
+  l.hostsim_level_seed.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+  l.hostsim_set_levels.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_uint64]
+  return l
 
 
 class Table:
@@ -97,17 +72,13 @@ class LevelSetEnv(HostSimEnv):
 
   def reset(self, mask=None):
     m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-    rc = lib().hostsim_levelset_reset(C.byref(self.cfg), C.byref(self.tb), C.byref(self.st), self.table.ptr, _p(m), self.pool, _ptr(self.obs))
+    rc = lib().hostsim_levelset_reset(C.byref(self.cfg), C.byref(self.tb), C.byref(self.st), self.table.ptr, _p(m), self.pool, _p(self.obs))
     assert rc == 0
     return self.obs
 
   def step(self, actions):
     a = np.ascontiguousarray(actions, np.int32)
-    rc = lib().hostsim_levelset_step(C.byref(self.cfg), C.byref(self.tb), C.byref(self.st), self.table.ptr, _ptr(a), _ptr(self.obs),
-                                     _ptr(self.reward), _ptr(self.done), self.pool)
+    rc = lib().hostsim_levelset_step(C.byref(self.cfg), C.byref(self.tb), C.byref(self.st), self.table.ptr, _p(a), _p(self.obs),
+                                     _p(self.reward), _p(self.done), self.pool)
     assert rc == 0
     return self.obs, self.reward, self.done
-
-
-if __name__ == '__main__':
-  print(build(force=True))

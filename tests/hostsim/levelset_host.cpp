@@ -1,14 +1,8 @@
 // TEST INFRASTRUCTURE -- level sets (csrc/env_levels.hpp: level_pick, set_levels_body, level_ids_body) on the CPU through WaveHost
 // (see wave_host.hpp), and Env.reset / a step with auto-reset / the pool's three generation stages WITH a level table: the
 // walks of hostsim.cpp's hostsim_reset and hostsim_step, handing the table to the bodies as the library's kernels do.
-#include <string.h>
-
-#include <vector>
-
-#include "wave_host.hpp"
-#include "../../crafter_amd/csrc/env_kernels.hpp"
+#include "walks.hpp"
 #include "../../crafter_amd/csrc/env_levels.hpp"
-#include "../../crafter_amd/csrc/launch_plan.hpp"
 
 using namespace crafter;
 
@@ -38,67 +32,34 @@ void hostsim_level_pick(const LevelTable* table, const uint64_t* lanes, const in
 
 uint32_t hostsim_level_seed(const LevelTable* table, uint64_t lane, int k) { return level_seed(table, lane, k); }
 
-static void run_generation(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const LevelTable* table, std::vector<uint8_t>& lds) {
-  int32_t* q = st->gen_q;
-  int count = q ? q[0] : 0;
-  if (count > gen_q_capacity(*cfg)) count = gen_q_capacity(*cfg);
-  for (int k = 0; k < count; k++) {
-    int env = q[4 + 2 * k], episode = q[4 + 2 * k + 1];
-    WaveHost w;
-    memset(lds.data(), 0xCD, lds.size());
-    gen_seed_body(w, lds.data(), env, episode, *cfg, *tb, *st, table);
-    for (int part = 0, parts = gen_classify_parts(*cfg); part < parts; part++) {
-      memset(lds.data(), 0xCD, lds.size());
-      gen_classify_body(w, lds.data(), env, episode, part, parts, *cfg, *tb, *st);
-    }
-    memset(lds.data(), 0xCD, lds.size());
-    gen_resolve_body(w, lds.data(), env, episode, 1u, *cfg, *tb, *st);
-  }
-  if (q) q[0] = 0;
-}
-
 int hostsim_levelset_reset(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const LevelTable* table, const uint8_t* mask,
                            int pool_mode, uint8_t* obs) {
-  std::vector<uint8_t> lds(lds_layout(*cfg).total + 64);
+  FakeLds lds = step_lds(*cfg);
   for (int env = 0; env < cfg->num_envs; env++) {
     if (mask && !mask[env]) continue;
-    memset(lds.data(), 0xCD, lds.size());
     WaveHost w;
-    reset_body(w, lds.data(), env, *cfg, *tb, *st, obs, pool_mode ? 0 : -1, table);
+    reset_body(w, lds.fresh(), env, *cfg, *tb, *st, obs, pool_mode ? 0 : -1, table);
   }
-  if (pool_mode) run_generation(cfg, tb, st, table, lds);
+  if (pool_mode) run_generation(*cfg, *tb, *st, lds, table);
   return 0;
 }
 
-// the fused step of the default geometry (one-byte slot ids), the regeneration queue, then (pool on) the generation batch
+// the fused step of the default geometry (one-byte slot ids; 1 for any other instance), the regeneration queue, then (pool on)
+// the generation batch
 int hostsim_levelset_step(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const LevelTable* table, const int32_t* actions,
                           uint8_t* obs, float* reward, uint8_t* done, int pool_mode) {
-  std::vector<uint8_t> lds(lds_layout(*cfg).total + frame_layout(*cfg).total + 64);
+  FakeLds lds = split_step_lds(*cfg);
   const LaunchPlan plan = launch_plan(*cfg, is_default_rules(*tb->rules));
   if (plan.instance != kInstance111 && plan.instance != kInstance110) return 1;
-  StepCtl ctl;
-  ctl.parity = 0;
-  ctl.gen_parity = pool_mode ? 0 : -1;
-  ctl.safe_seq = 0xffffffffu;
-  ctl.early_frame = 1;
-  static std::vector<uint32_t> noise_raw;
-  noise_raw.resize((size_t)cfg->num_envs * kNoiseStates * MT_N);
-  ctl.noise_raw = noise_raw.data();
-  for (int env = 0; env < cfg->num_envs; env++) {
-    memset(lds.data(), 0xCD, lds.size());
-    WaveHost w;
-    step_body<WaveHost, -1, 0, uint8_t>(w, lds.data(), env, *cfg, *tb, *st, actions, obs, reward, done, ctl);
-  }
+  static CtlScratch scratch;
+  const StepCtls c = make_ctls(*cfg, scratch, pool_mode ? 0 : -1, 1, true, false);
+  for (int env = 0; env < cfg->num_envs; env++) step_env(plan, false, c, lds, env, *cfg, *tb, *st, actions, obs, reward, done);
   if (cfg->auto_reset) {
-    int32_t* q = st->reset_q;
-    int count = q ? q[0] : 0;
-    for (int k = 0; k < count; k++) {
-      memset(lds.data(), 0xCD, lds.size());
+    drain_reset_q(*st, [&](int env) {
       WaveHost w;
-      reset_body(w, lds.data(), q[4 + k], *cfg, *tb, *st, obs, ctl.gen_parity, table);
-    }
-    if (q) q[0] = 0;
-    if (pool_mode) run_generation(cfg, tb, st, table, lds);
+      reset_body(w, lds.fresh(), env, *cfg, *tb, *st, obs, c.ctl.gen_parity, table);
+    });
+    if (pool_mode) run_generation(*cfg, *tb, *st, lds, table);
   }
   return 0;
 }

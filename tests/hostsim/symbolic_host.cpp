@@ -1,10 +1,5 @@
 // TEST INFRASTRUCTURE -- crafter_symbolic's body (csrc/symbolic.hpp) on the CPU through WaveHost (see wave_host.hpp).
-#include <string.h>
-
-#include <vector>
-
-#include "wave_host.hpp"
-#include "../../crafter_amd/csrc/launch_plan.hpp"   // LaunchPlan::maps_in_lds: the chooser between the two object paths, as the library's
+#include "walks.hpp"   // (launch_plan.hpp's LaunchPlan::maps_in_lds: the chooser between the two object paths, as the library's)
 #include "../../crafter_amd/csrc/symbolic.hpp"
 
 using namespace crafter;
@@ -15,16 +10,16 @@ int hostsim_symbolic_map_is_state(const Config* cfg) { return launch_plan(*cfg, 
 
 // cfg / tb / st: a HostSimEnv's.  local: [N][2][gw][gh] bytes or null, stats: [N][n_items + 4] floats or null.
 int hostsim_symbolic(const Config* cfg, const TablePtrs* tb, const StatePtrs* st, const uint8_t* mask, uint8_t* local, float* stats) {
-  std::vector<uint32_t> strip(symbolic_strip_bytes(*cfg) / 4);
+  FakeLds strip(symbolic_strip_bytes(*cfg) / 4 * 4);
   const bool map_is_state = !launch_plan(*cfg, false).maps_in_lds;
   // one env beyond the batch, as the last workgroup's spare waves: must return without touching anything
   for (int env = 0; env < cfg->num_envs + 1; env++) {
-    memset(strip.data(), 0xCD, strip.size() * 4);   // poisoned "LDS"
     WaveHost w;
+    uint8_t* lds = strip.fresh();
     if (map_is_state)
-      symbolic_body<WaveHost, 1>(w, (uint8_t*)strip.data(), env, *cfg, *tb, *st, mask, local, stats);
+      symbolic_body<WaveHost, 1>(w, lds, env, *cfg, *tb, *st, mask, local, stats);
     else
-      symbolic_body<WaveHost, 0>(w, (uint8_t*)strip.data(), env, *cfg, *tb, *st, mask, local, stats);
+      symbolic_body<WaveHost, 0>(w, lds, env, *cfg, *tb, *st, mask, local, stats);
   }
   return 0;
 }

@@ -4,40 +4,8 @@
 // heap block of exactly its size; runs the call once and prints one line per env,
 //   env status fnv(mat row) fnv(objs row) fnv(mt row) fnv(rec row) fnv(chunk_order row) fnv(census row) fnv(obs row)
 // which the test compares with the same call through the shared library.
-#include <stdio.h>
-#include <stdlib.h>
-
 #include "worlds_host.cpp"
-
-namespace {
-
-struct Blob {
-  std::vector<std::vector<uint8_t>> parts;
-  bool read(const char* path) {
-    FILE* f = fopen(path, "rb");
-    if (!f) return false;
-    uint64_t n = 0;
-    while (fread(&n, 8, 1, f) == 1) {
-      std::vector<uint8_t> p((size_t)n);
-      if (n && fread(p.data(), 1, (size_t)n, f) != (size_t)n) {
-        fclose(f);
-        return false;
-      }
-      parts.push_back(std::move(p));
-    }
-    fclose(f);
-    return true;
-  }
-};
-
-unsigned long long fnv(const void* p, size_t n) {
-  const uint8_t* b = (const uint8_t*)p;
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
-  return h;
-}
-
-}  // namespace
+#include "blob.hpp"
 
 int main(int argc, char** argv) {
   if (argc != 2) {
@@ -45,27 +13,18 @@ int main(int argc, char** argv) {
     return 2;
   }
   Blob b;
-  constexpr int kTables = (int)(sizeof(TablePtrs) / sizeof(void*)), kState = (int)(sizeof(StatePtrs) / sizeof(void*));
-  if (!b.read(argv[1]) || (int)b.parts.size() != 2 + kTables + kState + 6) {
+  // parts: [n_worlds, bank_max_objects] int32 | Config, tables, state (blob.hpp bind_env)
+  //        | mask | world_id | bank_mat | bank_objs | bank_nobj | bank_inv (empty: null)
+  Config cfg;
+  TablePtrs tb;
+  StatePtrs st;
+  if (!b.read(argv[1]) || (int)b.parts.size() != 1 + Blob::kEnvParts + 6 || !b.bind_env(1, cfg, tb, st)) {
     fprintf(stderr, "bad blob\n");
     return 2;
   }
-  // parts: [n_worlds, bank_max_objects] int32 | Config | the tables, in TablePtrs order | the state, in StatePtrs order (empty: null)
-  //        | mask | world_id | bank_mat | bank_objs | bank_nobj | bank_inv (empty: null)
   const int32_t* head = (const int32_t*)b.parts[0].data();
-  if (b.parts[1].size() != sizeof(Config)) return 2;
-  Config cfg;
-  memcpy(&cfg, b.parts[1].data(), sizeof(Config));
-  auto at = [&](int i) -> void* { return b.parts[i].empty() ? nullptr : b.parts[i].data(); };
-  void* tp[kTables];
-  for (int i = 0; i < kTables; i++) tp[i] = at(2 + i);
-  void* sp[kState];
-  for (int i = 0; i < kState; i++) sp[i] = at(2 + kTables + i);
-  TablePtrs tb;
-  StatePtrs st;
-  memcpy(&tb, tp, sizeof(tb));
-  memcpy(&st, sp, sizeof(st));
-  const int a0 = 2 + kTables + kState;
+  auto at = [&](int i) { return b.at(i); };
+  const int a0 = 1 + Blob::kEnvParts;
   const size_t n = (size_t)cfg.num_envs, frame = (size_t)cfg.size_w * cfg.size_h * 3, cells = (size_t)cfg.W * cfg.H;
   const size_t nch = (size_t)cfg.nchunk_x * cfg.nchunk_y;
   std::vector<uint8_t> obs(n * frame);
