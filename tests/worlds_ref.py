@@ -42,6 +42,12 @@ class AuthoredOracle(OracleEnv):
     super().__init__(**kw)
     self.world = world
     self.balance_events = 0   # spawns + despawns by the balance pass so far (the tests' preconditions)
+    self.refused_outside = []   # (step, type, tx, ty) of every move tried to a cell outside the map (the rim cases' witness)
+
+  def _try_move(self, slot, px, py, dx, dy, walkable):
+    if not self._inside(px + dx, py + dy):
+      self.refused_outside.append((self._step, self.otype[slot], px + dx, py + dy))
+    return super()._try_move(slot, px, py, dx, dy, walkable)
 
   def _balance_chunk(self, key):
     before = (len(self.otype), sum(1 for t in self.otype if t))

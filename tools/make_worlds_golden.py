@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Records tests/golden/reference_runs/authored_world.npz from the UNTOUCHED reference (imported through
+"""Records tests/golden/reference_runs/authored_world.npz and atlas.npz from the UNTOUCHED reference (imported through
 oracle/reference_harness.py), with its worldgen.generate_world replaced AT RUN TIME by the authored function of
 include/crafter_hip.h crafter_reset_worlds: write the map, World.add the objects in order, set the inventory.  Everything
-else -- Env.reset around the call, every step -- is the reference's own code.  The fixture is data only: one authored 64 x 64
-world (tests/worlds_cases.py meadow), its action tape, the state at the reset and at the end in full, a hash of every state
-field and of the frame at every step, and sampled frames in full (day and night).  tests/test_worlds_golden.py replays it
-against tests/worlds_ref.py AuthoredOracle, which is what the device code is compared with.  Run where the reference is:
+else -- Env.reset around the call, every step -- is the reference's own code.  The fixtures are data only: per authored
+64 x 64 world (tests/worlds_cases.py meadow; every case of tests/atlas_cases.py), its action tape, the state at the reset and
+at the end in full, a hash of every state field and of the frame at every step, and sampled frames in full (day and night).
+tests/test_worlds_golden.py replays it against tests/worlds_ref.py AuthoredOracle, which is what the device code is compared
+with (tests/test_atlas_golden.py: the atlas).  Run where the reference is:
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/make_worlds_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_worlds_golden.py [authored_world] [atlas]
 """
 import pathlib
 import sys
@@ -24,6 +25,7 @@ from make_golden import ref_state, sha  # noqa: E402
 from tests import worlds_cases as wc  # noqa: E402
 
 OUT = ROOT / 'tests' / 'golden' / 'reference_runs' / 'authored_world.npz'
+ATLAS = ROOT / 'tests' / 'golden' / 'reference_runs' / 'atlas.npz'
 CASE, SEED = 0, 31
 FIELDS = ('mat', 'objects', 'inventory', 'achievements', 'misc', 'chunk_order', 'mt_key', 'mt_pos')
 
@@ -57,44 +59,80 @@ def authored(crafter, world):
   return generate_world
 
 
-def main():
-  crafter = rh.load()
+def record(crafter, world, acts, seed, keep_frame, atlas=False):
+  """One episode of the reference in `world` along `acts` (atlas: stopped at the first done, with a hash of info['semantic']
+  at every step) -> the fixture's arrays: the tape, the reset and final state in full, a hash of every state field and of the
+  frame at every step, the frames `keep_frame(t, env)` picks in full."""
   from crafter import worldgen
-  world = wc.WORLDS[CASE]()
-  acts = np.array(wc.tape(CASE), np.int32)
-  env = crafter.Env(seed=SEED)
+  env = crafter.Env(seed=seed)
   original = worldgen.generate_world
   worldgen.generate_world = authored(crafter, world)
   try:
     obs = env.reset()
   finally:
     worldgen.generate_world = original
-  out = {'seed': np.int64(SEED), 'case': np.int32(CASE), 'actions': acts, 'reset_obs': obs}
+  out = {'actions': acts, 'reset_obs': obs}
   state = ref_state(env)
   for k in FIELDS:
     out['reset_' + k] = state[k]
   hashes = {k: [sha(state[k])] for k in FIELDS}
-  rewards, dones, obs_sha, frames, frame_steps = [], [], [sha(obs)], [], []
+  rewards, dones, obs_sha, sem_sha, frames, frame_steps = [], [], [sha(obs)], [np.uint64(0)], [], []
   for t, a in enumerate(acts):
-    obs, reward, done, _ = env.step(int(a))
+    obs, reward, done, info = env.step(int(a))
     rewards.append(reward)
     dones.append(bool(done))
     obs_sha.append(sha(obs))
+    sem_sha.append(sha(np.asarray(info['semantic'], np.uint8)))
     state = ref_state(env)
     for k in FIELDS:
       hashes[k].append(sha(state[k]))
-    if t % 30 == 0 or (env._step >= 148 and t % 8 == 0):
+    if keep_frame(t, env):
       frames.append(obs)
       frame_steps.append(t)
+    if done and atlas:
+      break
   for k in FIELDS:
     out['final_' + k] = state[k]
     out['sha_' + k] = np.array(hashes[k], np.uint64)
   out.update(rewards=np.array(rewards, np.float64), dones=np.array(dones, np.uint8), obs_sha=np.array(obs_sha, np.uint64),
-             frames=np.array(frames, np.uint8), frame_steps=np.array(frame_steps, np.int32))
-  OUT.parent.mkdir(parents=True, exist_ok=True)
-  np.savez_compressed(OUT, **out)
-  print(f'{OUT.name}: {len(acts)} steps, {len(frames)} full frames, {OUT.stat().st_size} bytes')
+             frames=np.array(frames, np.uint8).reshape((-1,) + obs.shape), frame_steps=np.array(frame_steps, np.int32))
+  if atlas:
+    out['sem_sha'] = np.array(sem_sha, np.uint64)
+  return out
+
+
+def save(path, out):
+  path.parent.mkdir(parents=True, exist_ok=True)
+  np.savez_compressed(path, **out)
+  print(f'{path.name}: {path.stat().st_size} bytes')
+
+
+def make_authored_world(crafter):
+  """authored_world.npz: the meadow through a night, sampled frames of day and night."""
+  acts = np.array(wc.tape(CASE), np.int32)
+  out = {'seed': np.int64(SEED), 'case': np.int32(CASE)}
+  out.update(record(crafter, wc.WORLDS[CASE](), acts, SEED, lambda t, env: t % 30 == 0 or (env._step >= 148 and t % 8 == 0)))
+  save(OUT, out)
+
+
+def make_atlas(crafter):
+  """atlas.npz: every case of the rule-branch atlas (tests/atlas_cases.py) at the default geometry, keys '<case>.<array>';
+  full frames only for the scripted steps of the cases whose point is a sprite."""
+  from tests import atlas_cases as ac
+  out = {'names': np.array(ac.NAMES), 'seeds': np.array(ac.SEEDS, np.int64)}
+  for name, seed in zip(ac.NAMES, ac.SEEDS):
+    acts = np.array(ac.tape(name), np.int32)
+    rec = record(crafter, ac.world(name), acts, seed, lambda t, env: name in ac.FRAME_CASES and t < len(ac.CASES[name][1]), atlas=True)
+    out.update({f'{name}.{k}': v for k, v in rec.items()})
+  save(ATLAS, out)
+
+
+def main(argv):
+  """No argument: both fixtures; otherwise the ones named (authored_world, atlas)."""
+  crafter = rh.load()
+  for name in argv or ['authored_world', 'atlas']:
+    {'authored_world': make_authored_world, 'atlas': make_atlas}[name](crafter)
 
 
 if __name__ == '__main__':
-  main()
+  main(sys.argv[1:])
