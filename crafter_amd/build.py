@@ -15,10 +15,13 @@ OUT = ROOT / '_lib' / 'libcrafter_hip.so'
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared']
 CFLAGS = [f for f in FLAGS if f != '-shared']
 ROLLOUT_FLAGS = ['-mllvm', '-disable-machine-licm']
+# The translation units of the library: (file name under csrc/, flags beyond CFLAGS).  sources(), build() and resource_usage() read this list.
+UNITS = [(SRC.name, []), (SRC_ROLLOUT.name, ROLLOUT_FLAGS), (SRC_SUBSET.name, []), (SRC_ROLLOUT_SUBSET.name, ROLLOUT_FLAGS),
+         ('crafter_exchange.hip', [])]   # the RCCL exchange: host code only
 
 
 def sources():
-  return ([SRC, SRC_ROLLOUT, SRC_SUBSET, SRC_ROLLOUT_SUBSET] + sorted((ROOT / 'csrc').glob('*.hpp')) + sorted((ROOT / 'csrc').glob('*.inc')) +
+  return ([ROOT / 'csrc' / name for name, _ in UNITS] + sorted((ROOT / 'csrc').glob('*.hpp')) + sorted((ROOT / 'csrc').glob('*.inc')) +
           [ROOT.parent / 'include' / 'crafter_hip.h', ROOT.parent / 'include' / 'crafter_hip_types.h'])
 
 
@@ -44,8 +47,7 @@ def build(force=False, verbose=False, out=None, defines=(), root=None):
   target = pathlib.Path(out) if out else OUT
   target.parent.mkdir(exist_ok=True)
   csrc = ROOT / 'csrc' if root is None else pathlib.Path(root) / 'crafter_amd' / 'csrc'
-  units = [(csrc / SRC.name, []), (csrc / SRC_ROLLOUT.name, ROLLOUT_FLAGS), (csrc / SRC_SUBSET.name, []),
-           (csrc / SRC_ROLLOUT_SUBSET.name, ROLLOUT_FLAGS)]
+  units = [(csrc / name, extra) for name, extra in UNITS if root is None or (csrc / name).exists()]   # (an older tree may lack a unit)
   dflags = [f'-D{d}' for d in defines]
   import tempfile
   from concurrent.futures import ThreadPoolExecutor
@@ -73,16 +75,28 @@ if __name__ == '__main__':
   print(build(force=True, verbose=True))
 
 
+_usage = None   # resource_usage()'s parsed result: the units compile once per process
+
+
 def resource_usage():
   """{kernel name: {'vgprs', 'scratch', 'occupancy', ...}} from -Rpass-analysis=kernel-resource-usage
-  (compiles to a throw-away object; used by the tests to keep the step kernel free of scratch)."""
+  (compiles to a throw-away object; used by the tests to keep the step kernel free of scratch).
+  Every call returns a copy of its own."""
+  import copy
+  global _usage
+  if _usage is None:
+    _usage = _compile_resource_usage()
+  return copy.deepcopy(_usage)
+
+
+def _compile_resource_usage():
   import re
   import tempfile
   hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
   text = ''
   with tempfile.TemporaryDirectory() as tmp:
-    for src, extra in ((SRC, []), (SRC_ROLLOUT, ROLLOUT_FLAGS), (SRC_SUBSET, []), (SRC_ROLLOUT_SUBSET, ROLLOUT_FLAGS)):
-      cmd = [hipcc] + CFLAGS + extra + ['-Rpass-analysis=kernel-resource-usage', '-c', '-o', str(pathlib.Path(tmp) / 'x.o'), str(src)]
+    for name, extra in UNITS:
+      cmd = [hipcc] + CFLAGS + extra + ['-Rpass-analysis=kernel-resource-usage', '-c', '-o', str(pathlib.Path(tmp) / 'x.o'), str(ROOT / 'csrc' / name)]
       proc = subprocess.run(cmd, capture_output=True, text=True)
       if proc.returncode != 0:
         raise RuntimeError(proc.stderr)

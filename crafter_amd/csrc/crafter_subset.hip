@@ -27,7 +27,7 @@ crafter_step_envs_check_kernel(SubsetCheck c) {
   step_envs_check_body(CheckThreads{}, c, flags);
 }
 
-// Workgroup b steps env idx[b]: crafter_step_kernel's body (crafter_hip.hip) and launch bounds, instance by instance.
+// Workgroup b steps env idx[b]: crafter_step_kernel's body (entry_kernels.hpp) and launch bounds, instance by instance.
 #ifndef CRAFTER_BIG_WAVES
 #define CRAFTER_BIG_WAVES 6
 #endif

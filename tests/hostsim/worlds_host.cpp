@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE -- crafter_reset_worlds on the CPU through WaveHost (see wave_host.hpp): the host-side refusals of the
 // entry point and the kernel's body (csrc/env_worlds.hpp reset_world_body), one env after the other, each in freshly poisoned
 // "LDS" of exactly the size the library launches with (launch_plan's reset_lds).  The reset kernel's pool tail is the library's
-// own (crafter_hip.hip) and is not played here: the harness runs with the world pool off.
+// own (csrc/entry_kernels.hpp reset_pool_tail) and is not played here: the harness runs with the world pool off.
 #include <string.h>
 
 #include <vector>

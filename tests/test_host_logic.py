@@ -198,6 +198,21 @@ def test_step_kernel_stays_out_of_scratch():
     assert usage[k]['vgprs'] <= 128, (k, usage[k])
 
 
+def test_build_reads_one_unit_table():
+  """build.UNITS is the one list of translation units: every csrc/*.hip is on it, sources() (the staleness check and the
+  source hash) sees every unit and every header, and resource_usage() hands each caller a dictionary of its own."""
+  from crafter_amd import build
+  csrc = build.ROOT / 'csrc'
+  units = {name for name, _ in build.UNITS}
+  assert {p.name for p in csrc.glob('*.hip')} <= units
+  srcs = set(build.sources())
+  assert {csrc / name for name in units} <= srcs
+  assert set(csrc.glob('*.hpp')) <= srcs
+  a, b = build.resource_usage(), build.resource_usage()
+  assert a == b and a is not b
+  assert all(a[k] is not b[k] for k in a)
+
+
 def test_compiled_in_default_rules_are_current():
   """csrc/default_rules.inc (the step kernel's compile-time rules) is what tables.build_rules makes of data/rules.json."""
   import importlib.util
