@@ -22,6 +22,15 @@ class CrafterDeviceError(RuntimeError):
   pass
 
 
+def _ptr(t):
+  """A tensor's address as the void* the C ABI takes; None (an argument left out) stays None."""
+  return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _on_device(t):
+  return torch.is_tensor(t) and t.is_cuda
+
+
 class EnvStore:
   """Copies of env rows taken by BatchedEnv.save_state: each env's state (no world-pool buffers, no queues) and its last obs /
   reward / done, in device tensors (or host tensors after .cpu(), e.g. for pickling), with the geometry they were taken with.
@@ -65,16 +74,17 @@ class _Handle:
     with torch.cuda.device(device):
       if lib.crafter_create(C.byref(cfg), C.byref(self.ptr)):
         raise CrafterDeviceError(_libmod.last_error(lib, None))
-      t = host_tables
-      self._rules_buf = t.rules_bytes()
-      p = lambda a: a.ctypes.data_as(C.c_void_p)
-      ht = _libmod.HostTablesC(
-          rules=p(self._rules_buf), atlas=p(t.atlas), atlas_bytes=t.atlas.nbytes,
-          tex_tile=p(t.tex_tile), n_tex_tile=t.tex_tile.size, tex_icon=p(t.tex_icon), n_tex_icon=t.tex_icon.size,
-          tex_digit=p(t.tex_digit), n_tex_digit=t.tex_digit.size, tex_alpha=p(t.tex_alpha),
-          n_tex_alpha=t.tex_alpha.size, item_pos=p(t.item_pos), n_item_pos=t.item_pos.size,
-          daylight=p(t.daylight), n_daylight=t.daylight.size, vignette=p(t.vignette),
-          n_vignette=t.vignette.size, unit255=p(t.unit255), n_unit255=t.unit255.size)
+      self._rules_buf = host_tables.rules_bytes()
+      ht = _libmod.HostTablesC()
+      for name, ctype in ht._fields_:
+        if name == 'rules':
+          ht.rules = self._rules_buf.ctypes.data
+        elif name == 'atlas_bytes':
+          ht.atlas_bytes = host_tables.atlas.nbytes
+        elif ctype is C.c_void_p:   # table x of the host tables, followed by its length n_x
+          setattr(ht, name, getattr(host_tables, name).ctypes.data)
+        else:
+          setattr(ht, name, getattr(host_tables, name[2:]).size)
       self.check(lib.crafter_upload_tables(self.ptr, C.byref(ht)))
 
   def check(self, rc):
@@ -129,10 +139,15 @@ class BatchedEnv:
     self._native = _Handle(self._lib, self.cfg, self.tables, self.device)
     self._handle = self._native.ptr
     self._aux = {}   # render(size) handles for other frame sizes, bound to the same state
+    self._levels = None   # set_levels: the level table's device tensors
+    self._final = None   # final_buffers: what step(final=True) writes
+    self._prof = None   # enable_phase_stamps: the stamp buffer
+    self._timing_on = False
+    self.objects_grown = 0   # times _grow_objects doubled the slot table
+    self._keep = None   # the tensors of the last call enqueued: alive until the next one
     with torch.cuda.device(self.device):
       self._alloc_state()
     self._pool_warned = False
-    self._levels = None   # set_levels: the level table's device tensors
     self.grow_objects = bool(grow_objects)   # check_errors() doubles the slot table before an env can fill it (_grow_objects)
     # Env(length=None): no episode may outrun the daylight table (_grow_daylight).  _step_bound >= every env's step counter.
     self._unbounded = self.cfg.length == 0
@@ -175,7 +190,7 @@ class BatchedEnv:
     ptrs = {k: v.data_ptr() for k, v in self.state.items()}
     for name in ('semantic', 'prof') + state.POOL_BUFFERS:
       ptrs.setdefault(name, None)
-    if getattr(self, '_prof', None) is not None:
+    if self._prof is not None:
       ptrs['prof'] = self._prof.data_ptr()
     return abi.StatePtrs(**ptrs)
 
@@ -186,7 +201,43 @@ class BatchedEnv:
     mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
     if check_len and mask.numel() != self.num_envs:
       raise ValueError(f'mask must have {self.num_envs} elements')
-    return mask, C.c_void_p(mask.data_ptr())
+    return mask, _ptr(mask)
+
+  def _call(self, fn, *args, handle=None):
+    """Every entry point that takes a stream: fn(handle, *args, the current torch stream) with the batch's device current;
+    a non-zero return raises CrafterDeviceError.  handle: a _Handle other than the batch's own (render at another size)."""
+    h = handle or self._native
+    with torch.cuda.device(self.device):
+      h.check(fn(h.ptr, *args, self._stream()))
+
+  def _out(self, t, shape, dtype, what='out', align16=False):
+    """The one check of a tensor the caller gives a kernel to write: a contiguous tensor of exactly this dtype and shape on
+    the batch's device (align16: at a 16-byte aligned address).  ValueError otherwise, before anything is enqueued.  -> t"""
+    if not (torch.is_tensor(t) and t.device == self.device and t.dtype == dtype and tuple(t.shape) == tuple(shape) and
+            t.is_contiguous() and not (align16 and t.data_ptr() % 16)):
+      raise ValueError(f'{what} must be a contiguous{", 16-byte aligned" if align16 else ""} {dtype} tensor of shape '
+                       f'{tuple(shape)} on {self.device}')
+    return t
+
+  def _step_out(self, out):
+    """-> (obs, reward, done) a step writes: the batch's own, or the 16-byte aligned tensors of out = (obs or None, reward, done)."""
+    if out is None:
+      return self.obs, self.reward, self.done
+    o, r, d = out
+    like = lambda t, mine, what: self._out(t, mine.shape, mine.dtype, what, align16=True)
+    return (self.obs if o is None else like(o, self.obs, 'out[0]')), like(r, self.reward, 'out[1]'), like(d, self.done, 'out[2]')
+
+  def _rollout_out(self, T, n, out, obs):
+    """-> (o, r, d) a rollout of T steps of n envs writes: u8[T,n,H,W,3] or None, f32[T,n], u8[T,n].  out None: new tensors,
+    without frames if obs is false or the batch has render=False (no kernel draws, there is no frame to return).  Otherwise
+    the 16-byte aligned tensors of out = (obs or None, reward, done); an obs tensor given there is written whatever `obs` says."""
+    frames, scalars = ((T, n) + tuple(self.obs.shape[1:]), torch.uint8), ((T, n), torch.float32)
+    if out is None:
+      new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+      return (new(*frames) if obs and self.cfg.render_obs else None), new(*scalars), new((T, n), torch.uint8)
+    o, r, d = out
+    return (None if o is None else self._out(o, *frames, 'out[0]', align16=True),
+            self._out(r, *scalars, 'out[1]', align16=True), self._out(d, (T, n), torch.uint8, 'out[2]', align16=True))
 
   def _actions(self, actions):
     """-> contiguous int32 device tensor"""
@@ -295,11 +346,11 @@ class BatchedEnv:
     self._native, self._handle = native, native.ptr
     self.cfg = cfg
     self._ctor['max_objects'] = new_max
-    self.objects_grown = getattr(self, 'objects_grown', 0) + 1
-    if getattr(self, '_timing_on', False):   # handle-level settings move with the handle
+    self.objects_grown += 1
+    if self._timing_on:   # handle-level settings move with the handle
       with torch.cuda.device(self.device):
         self._check(self._lib.crafter_set_timing(self._handle, 1))
-    if getattr(self, '_levels', None) is not None:   # ... and so does the level table
+    if self._levels is not None:   # ... and so does the level table
       self._enqueue_levels()
     if was_default:
       import warnings
@@ -321,46 +372,45 @@ class BatchedEnv:
     its env as it was and sets ST_BAD_WORLD (check_errors).  The slot table grows first if the bank's longest world would fill
     three quarters of it (_grow_objects).  No host round trip: with auto_reset=False, `step(); reset(mask=done, worlds=bank,
     world_ids=ids)` keeps every env in authored worlds."""
-    if world_ids is not None and worlds is None:
-      raise ValueError('world_ids without worlds')
-    if worlds is not None:
-      if not hasattr(self._lib, 'crafter_reset_worlds'):
-        raise _libmod.CrafterLibError('the loaded library has no crafter_reset_worlds (an older build): authored worlds are not available')
-      if tuple(worlds.area) != (int(self.cfg.W), int(self.cfg.H)):
-        raise ValueError(f'the bank holds {worlds.area[0]} x {worlds.area[1]} worlds, the batch {self.cfg.W} x {self.cfg.H}')
-      if worlds.inv is not None and worlds.inv.shape[1] != len(self.item_names):
-        raise ValueError('the bank was made for rules with another number of items')
-      ids = None
-      if torch.is_tensor(world_ids) and world_ids.is_cuda:
-        if world_ids.dtype != torch.int32 or tuple(world_ids.shape) != (self.num_envs,) or world_ids.device != self.device:
-          raise ValueError(f'world_ids on the device must be an int32 tensor of shape [{self.num_envs}] on {self.device}')
-        ids = world_ids.contiguous()
-      elif world_ids is not None:
-        a = np.asarray(world_ids.cpu() if torch.is_tensor(world_ids) else world_ids).reshape(-1)
-        if a.size != self.num_envs or (a.size and not np.issubdtype(a.dtype, np.integer)):
-          raise ValueError(f'world_ids must be {self.num_envs} integers')
-        if a.size and (a.min() < 0 or a.max() >= len(worlds)):
-          raise ValueError(f'world_ids must lie in 0 .. {len(worlds) - 1}')
-        ids = torch.from_numpy(a.astype(np.int32)).to(self.device)
-      if self.grow_objects and 4 * worlds.max_objects > 3 * self.cfg.max_objects:   # (check_errors' own rule, ahead of the reset)
-        self._grow_objects(max(2 * self.cfg.max_objects, 2 * worlds.max_objects))
-    if seeds is not None or episodes is not None:
-      kept = self._reseed(seeds, episodes, mask)
-    else:
-      kept = None
+    ids = self._world_ids(worlds, world_ids)
+    if worlds is not None and self.grow_objects and 4 * worlds.max_objects > 3 * self.cfg.max_objects:   # (check_errors' own rule, ahead of the reset)
+      self._grow_objects(max(2 * self.cfg.max_objects, 2 * worlds.max_objects))
+    kept = self._reseed(seeds, episodes, mask) if seeds is not None or episodes is not None else None
     mask, mptr = self._mask(mask, check_len=worlds is not None)
-    with torch.cuda.device(self.device):
-      if worlds is None:
-        self._check(self._lib.crafter_reset(self._handle, mptr, C.c_void_p(self.obs.data_ptr()), self._stream()))
-      else:
-        t = worlds.device_tensors(self.device)
-        self._check(self._lib.crafter_reset_worlds(
-            self._handle, mptr, None if ids is None else C.c_void_p(ids.data_ptr()), C.c_void_p(t['mat'].data_ptr()),
-            C.c_void_p(t['objs'].data_ptr()), C.c_void_p(t['nobj'].data_ptr()), None if t['inv'] is None else C.c_void_p(t['inv'].data_ptr()),
-            len(worlds), int(worlds.objs.shape[1]), C.c_void_p(self.obs.data_ptr()), self._stream()))
-        kept = (kept, worlds, t, ids)
+    if worlds is None:
+      self._call(self._lib.crafter_reset, mptr, _ptr(self.obs))
+    else:
+      t = worlds.device_tensors(self.device)
+      self._call(self._lib.crafter_reset_worlds, mptr, _ptr(ids), _ptr(t['mat']), _ptr(t['objs']), _ptr(t['nobj']), _ptr(t['inv']),
+                 len(worlds), int(worlds.objs.shape[1]), _ptr(self.obs))
+      kept = (kept, worlds, t, ids)
     self._keep = mask if kept is None else (mask, kept)
     return self.obs
+
+  def _world_ids(self, worlds, world_ids):
+    """reset()'s checks of a WorldBank and the ids into it -> world_ids as an int32 device tensor [num_envs], or None (no bank,
+    or env i into world i % len(worlds)).  Host ids are range-checked here; device ids are not read back."""
+    if worlds is None:
+      if world_ids is not None:
+        raise ValueError('world_ids without worlds')
+      return None
+    _libmod.require(self._lib, 'crafter_reset_worlds', 'authored worlds')
+    if tuple(worlds.area) != (int(self.cfg.W), int(self.cfg.H)):
+      raise ValueError(f'the bank holds {worlds.area[0]} x {worlds.area[1]} worlds, the batch {self.cfg.W} x {self.cfg.H}')
+    if worlds.inv is not None and worlds.inv.shape[1] != len(self.item_names):
+      raise ValueError('the bank was made for rules with another number of items')
+    if world_ids is None:
+      return None
+    if _on_device(world_ids):
+      if world_ids.dtype != torch.int32 or tuple(world_ids.shape) != (self.num_envs,) or world_ids.device != self.device:
+        raise ValueError(f'world_ids on the device must be an int32 tensor of shape [{self.num_envs}] on {self.device}')
+      return world_ids.contiguous()
+    a = np.asarray(world_ids.cpu() if torch.is_tensor(world_ids) else world_ids).reshape(-1)
+    if a.size != self.num_envs or (a.size and not np.issubdtype(a.dtype, np.integer)):
+      raise ValueError(f'world_ids must be {self.num_envs} integers')
+    if a.size and (a.min() < 0 or a.max() >= len(worlds)):
+      raise ValueError(f'world_ids must lie in 0 .. {len(worlds) - 1}')
+    return torch.from_numpy(a.astype(np.int32)).to(self.device)
 
   def export_worlds(self, idx=None):
     """The current worlds of envs idx (all by default) as host arrays, in exactly the form WorldBank accepts --
@@ -378,67 +428,87 @@ class BatchedEnv:
   MAX_EPISODE = 2 ** 31 - 3   # the world pool asks for episode + 2
 
   @staticmethod
+  def _host_values(x):
+    """A host sequence, numpy array or CPU tensor as a list of Python values."""
+    return x.tolist() if torch.is_tensor(x) or isinstance(x, np.ndarray) else list(x)
+
+  @staticmethod
+  def _lanes_arg(seeds, n=None):
+    """seeds -> their 64 lane bits: the int64 / uint64 device tensor given, checked for dtype and shape ([n]; any length when
+    n is None) and never read back, or the uint64 numpy array hashed from host values (n of them, when n is given)."""
+    if _on_device(seeds):
+      if seeds.dtype not in (torch.int64, getattr(torch, 'uint64', torch.int64)) or seeds.dim() != 1 or n not in (None, seeds.shape[0]):
+        raise ValueError(f'seeds on the device must be a one-dimensional int64 / uint64 tensor{"" if n is None else f" of shape [{n}]"} '
+                         '(the 64 lane bits)')
+      return seeds
+    seeds = BatchedEnv._host_values(seeds)
+    if n is not None and len(seeds) != n:
+      raise ValueError(f'len(seeds) is {len(seeds)}, the batch has {n} envs')
+    return state.seed_lanes(seeds)
+
+  @staticmethod
+  def _episodes_arg(episodes, n, what):
+    """episodes -> None (1 everywhere), the int32 device tensor [n] given (dtype and shape checked, never read back), or an
+    int32 numpy array [n] of host values: one int for all, or n integers in 1 .. MAX_EPISODE.  `what` says in the message what
+    has n entries."""
+    if episodes is None:
+      return None
+    if _on_device(episodes):
+      if episodes.dtype != torch.int32 or tuple(episodes.shape) != (n,):
+        raise ValueError(f'episodes on the device must be an int32 tensor of shape [{n}]')
+      return episodes
+    a = np.asarray(episodes.cpu() if torch.is_tensor(episodes) else episodes)
+    if a.ndim == 0:
+      a = np.full(n, a[()])
+    a = a.reshape(-1)
+    if a.size != n:
+      raise ValueError(f'len(episodes) is {a.size}, {what}')
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+      raise ValueError('episodes must be integers')
+    if a.size and (a.min() < 1 or a.max() > BatchedEnv.MAX_EPISODE):
+      raise ValueError(f'episodes must lie in 1 .. {BatchedEnv.MAX_EPISODE}')
+    return a.astype(np.int32)
+
+  @staticmethod
   def _check_levels(num_envs, seeds, episodes):
     """The host side of reseed(), callable without a device: -> (lanes, episodes), each a numpy array (uint64 / int32
     [num_envs]) made of host values, the device tensor that was given, or None.  Host values are checked here and raise
     ValueError before anything is enqueued; device tensors are only checked for dtype and shape (never read back)."""
-    def on_device(t):
-      return torch.is_tensor(t) and t.is_cuda
-    lanes = None
-    if on_device(seeds):
-      if seeds.dtype not in (torch.int64, getattr(torch, 'uint64', torch.int64)) or tuple(seeds.shape) != (num_envs,):
-        raise ValueError(f'seeds on the device must be an int64 / uint64 tensor of shape [{num_envs}] (the 64 lane bits)')
-      lanes = seeds
-    elif seeds is not None:
-      seeds = seeds.tolist() if torch.is_tensor(seeds) or isinstance(seeds, np.ndarray) else list(seeds)
-      if len(seeds) != num_envs:
-        raise ValueError(f'len(seeds) is {len(seeds)}, the batch has {num_envs} envs')
-      lanes = state.seed_lanes(seeds)
-    eps = None
-    if on_device(episodes):
-      if episodes.dtype != torch.int32 or tuple(episodes.shape) != (num_envs,):
-        raise ValueError(f'episodes on the device must be an int32 tensor of shape [{num_envs}]')
-      eps = episodes
-    elif episodes is not None:
-      a = np.asarray(episodes.cpu() if torch.is_tensor(episodes) else episodes)
-      if a.ndim == 0:
-        a = np.full(num_envs, a[()])
-      a = a.reshape(-1)
-      if a.size != num_envs:
-        raise ValueError(f'len(episodes) is {a.size}, the batch has {num_envs} envs')
-      if a.size and not np.issubdtype(a.dtype, np.integer):
-        raise ValueError('episodes must be integers')
-      if a.size and (a.min() < 1 or a.max() > BatchedEnv.MAX_EPISODE):
-        raise ValueError(f'episodes must lie in 1 .. {BatchedEnv.MAX_EPISODE}')
-      eps = a.astype(np.int32)
-    return lanes, eps
+    lanes = None if seeds is None else BatchedEnv._lanes_arg(seeds, num_envs)
+    return lanes, BatchedEnv._episodes_arg(episodes, num_envs, f'the batch has {num_envs} envs')
 
-  def _reseed(self, seeds, episodes, mask):
-    if not hasattr(self._lib, 'crafter_reseed'):
-      raise _libmod.CrafterLibError('the loaded library has no crafter_reseed (an older build): level selection is not available')
-    if seeds is not None and not (torch.is_tensor(seeds) and seeds.is_cuda):
-      seeds = seeds.tolist() if torch.is_tensor(seeds) or isinstance(seeds, np.ndarray) else list(seeds)
-    lanes, eps = self._check_levels(self.num_envs, seeds, episodes)
-    host_seeds = seeds if isinstance(seeds, list) else None
-    host_mask = None
-    if mask is not None and not (torch.is_tensor(mask) and mask.is_cuda):
-      host_mask = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).reshape(-1) != 0
-    dmask, mptr = self._mask(mask, check_len=True)
+  def _level_tensors(self, lanes, eps, default_eps=None):
+    """What _check_levels / _check_level_set return, as contiguous device tensors (lanes int64, eps int32).  Host arrays are
+    uploaded; device tensors are passed through -- not copied -- and must be on the batch's device.  eps None: default_eps in
+    every entry, or None if that is None too."""
     for t in (lanes, eps):
       if torch.is_tensor(t) and t.device != self.device:
         raise ValueError(f'level tensor on {t.device}, batch on {self.device}')
     with torch.cuda.device(self.device):
-      if lanes is None:   # episodes alone: the rows keep their lanes
-        o = self._off['seed_lane']
-        lanes = self._rec_i32[:, o:o + 2].contiguous().view(torch.int64).reshape(-1)
-      elif torch.is_tensor(lanes):
-        lanes = lanes.contiguous()
+      if torch.is_tensor(lanes):
+        lanes = lanes.contiguous().view(torch.int64)
       else:
         lanes = torch.from_numpy(lanes.view(np.int64)).to(self.device)
       if eps is not None:
         eps = eps.contiguous() if torch.is_tensor(eps) else torch.from_numpy(eps).to(self.device)
-      self._check(self._lib.crafter_reseed(self._handle, mptr, C.c_void_p(lanes.data_ptr()),
-                                           None if eps is None else C.c_void_p(eps.data_ptr()), self._stream()))
+      elif default_eps is not None:
+        eps = torch.full((lanes.numel(),), default_eps, dtype=torch.int32, device=self.device)
+    return lanes, eps
+
+  def _reseed(self, seeds, episodes, mask):
+    fn = _libmod.require(self._lib, 'crafter_reseed', 'level selection')
+    if seeds is not None and not _on_device(seeds):
+      seeds = self._host_values(seeds)
+    lanes, eps = self._check_levels(self.num_envs, seeds, episodes)
+    host_seeds = seeds if isinstance(seeds, list) else None
+    host_mask = None
+    if mask is not None and not _on_device(mask):
+      host_mask = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).reshape(-1) != 0
+    dmask, mptr = self._mask(mask, check_len=True)
+    if lanes is None:   # episodes alone: the rows keep their lanes
+      lanes = self._record_lanes()
+    lanes, eps = self._level_tensors(lanes, eps)
+    self._call(fn, mptr, _ptr(lanes), _ptr(eps))
     if seeds is not None:   # self.seeds: what the host knows
       if host_mask is not None:
         for i in np.nonzero(host_mask)[0]:
@@ -476,12 +546,15 @@ class BatchedEnv:
     With a level table set (set_levels) the pair is (table seed lane, table episode) of level_ids(): the levels actually
     played, and the promise still holds for reset(seeds=lanes, episodes=episode) on a batch WITHOUT a table.  As for
     level_ids(), a row is exact if its episode in progress began while this table was set."""
-    if getattr(self, '_levels', None) is not None:
+    if self._levels is not None:
       ids = self.level_ids().to(torch.int64)
       return self._levels['lanes'][ids], self._levels['episodes'][ids]
+    return self._record_lanes(), self._rec_i32[:, self._off['episode']].clone()
+
+  def _record_lanes(self):
+    """int64 [N]: a device copy of every env's seed lane."""
     o = self._off['seed_lane']
-    lanes = self._rec_i32[:, o:o + 2].contiguous().view(torch.int64).reshape(-1)
-    return lanes, self._rec_i32[:, self._off['episode']].clone()
+    return self._rec_i32[:, o:o + 2].contiguous().view(torch.int64).reshape(-1)
 
   # ------------------------------------------------------------------ level sets (include/crafter_hip.h crafter_set_levels)
   MAX_LEVELS = state.MAX_LEVELS
@@ -492,34 +565,11 @@ class BatchedEnv:
     device tensor given; episodes: int32 numpy [K], the device tensor given, or None (1); cum: uint32 numpy [K] or None; key:
     the 64 key bits.  Host values are checked here and raise ValueError before anything is enqueued; device tensors are only
     checked for dtype and shape."""
-    def on_device(t):
-      return torch.is_tensor(t) and t.is_cuda
-    if on_device(seeds):
-      if seeds.dtype not in (torch.int64, getattr(torch, 'uint64', torch.int64)) or seeds.dim() != 1:
-        raise ValueError('seeds on the device must be a one-dimensional int64 / uint64 tensor (the 64 lane bits)')
-      lanes, K = seeds, int(seeds.shape[0])
-    else:
-      seeds = seeds.tolist() if torch.is_tensor(seeds) or isinstance(seeds, np.ndarray) else list(seeds)
-      lanes, K = state.seed_lanes(seeds), len(seeds)
+    lanes = BatchedEnv._lanes_arg(seeds)
+    K = len(lanes)
     if not 1 <= K <= BatchedEnv.MAX_LEVELS:
       raise ValueError(f'a level table holds 1 .. {BatchedEnv.MAX_LEVELS} levels, got {K}')
-    eps = None
-    if on_device(episodes):
-      if episodes.dtype != torch.int32 or tuple(episodes.shape) != (K,):
-        raise ValueError(f'episodes on the device must be an int32 tensor of shape [{K}]')
-      eps = episodes
-    elif episodes is not None:
-      a = np.asarray(episodes.cpu() if torch.is_tensor(episodes) else episodes)
-      if a.ndim == 0:
-        a = np.full(K, a[()])
-      a = a.reshape(-1)
-      if a.size != K:
-        raise ValueError(f'len(episodes) is {a.size}, the table has {K} levels')
-      if not np.issubdtype(a.dtype, np.integer):
-        raise ValueError('episodes must be integers')
-      if a.min() < 1 or a.max() > BatchedEnv.MAX_EPISODE:
-        raise ValueError(f'episodes must lie in 1 .. {BatchedEnv.MAX_EPISODE}')
-      eps = a.astype(np.int32)
+    eps = BatchedEnv._episodes_arg(episodes, K, f'the table has {K} levels')
     cum = None
     if weights is not None:
       w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights).reshape(-1)
@@ -531,13 +581,10 @@ class BatchedEnv:
   def _enqueue_levels(self):
     """crafter_set_levels with the table the batch keeps (None: clear)."""
     t = self._levels
-    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-    with torch.cuda.device(self.device):
-      if t is None:
-        self._check(self._lib.crafter_set_levels(self._handle, None, None, None, 0, 0, self._stream()))
-      else:
-        self._check(self._lib.crafter_set_levels(self._handle, p(t['lanes']), p(t['episodes']), p(t['cum']), int(t['lanes'].numel()),
-                                                 t['key'], self._stream()))
+    if t is None:
+      self._call(self._lib.crafter_set_levels, None, None, None, 0, 0)
+    else:
+      self._call(self._lib.crafter_set_levels, _ptr(t['lanes']), _ptr(t['episodes']), _ptr(t['cum']), int(t['lanes'].numel()), t['key'])
 
   def set_levels(self, seeds, episodes=None, weights=None, key=0):
     """Sets the batch's LEVEL TABLE: K levels (seeds[j], episodes[j]), each the episode a fresh crafter.Env(seed=seeds[j]) shows
@@ -561,8 +608,7 @@ class BatchedEnv:
     With a table set, reseed() / reset(seeds=, episodes=) choose an env's position in its draw sequence, not its level:
     held-out evaluation on the same batch clears the table first.  copy_envs / save_state / load_state carry lane and episode
     count, so a copy plays the levels its source would; a store loaded under another table follows that table."""
-    if not hasattr(self._lib, 'crafter_set_levels'):
-      raise _libmod.CrafterLibError('the loaded library has no crafter_set_levels (an older build): level sets are not available')
+    _libmod.require(self._lib, 'crafter_set_levels', 'level sets')
     if seeds is None:
       if episodes is not None or weights is not None:
         raise ValueError('set_levels(None) clears the table: episodes / weights need seeds')
@@ -570,20 +616,12 @@ class BatchedEnv:
       self._enqueue_levels()
       return
     lanes, eps, cum, key = self._check_level_set(seeds, episodes, weights, key)
-    for t in (lanes, eps):
-      if torch.is_tensor(t) and t.device != self.device:
-        raise ValueError(f'level tensor on {t.device}, batch on {self.device}')
-    with torch.cuda.device(self.device):
-      if torch.is_tensor(lanes):
-        lanes = lanes.contiguous().view(torch.int64).clone()
-      else:
-        lanes = torch.from_numpy(lanes.view(np.int64)).to(self.device)
-      K = int(lanes.numel())
-      if eps is None:
-        eps = torch.ones(K, dtype=torch.int32, device=self.device)
-      else:
-        eps = eps.contiguous().clone() if torch.is_tensor(eps) else torch.from_numpy(eps).to(self.device)
-      cum_t = None if cum is None else torch.from_numpy(cum.view(np.int32)).to(self.device)   # (the 32 bits of each uint32)
+    lanes, eps = self._level_tensors(lanes, eps, default_eps=1)
+    if _on_device(seeds):   # the batch keeps the table: tensors of the caller's are copied
+      lanes = lanes.clone()
+    if _on_device(episodes):
+      eps = eps.clone()
+    cum_t = None if cum is None else torch.from_numpy(cum.view(np.int32)).to(self.device)   # (the 32 bits of each uint32)
     self._levels = {'lanes': lanes, 'episodes': eps, 'cum': cum_t, 'key': key, 'cum_host': cum}
     self._enqueue_levels()
 
@@ -594,16 +632,13 @@ class BatchedEnv:
     The exact use: after a step(), the ids of the rows with done != 0 are the levels of the episodes that just began; a
     level-replay loop keeps its own [N] tensor of them.  Read-only, no wait for the world pool.  mask: rows with a zero byte
     are left untouched.  out: a contiguous int32 device tensor [N] to write into."""
-    if not hasattr(self._lib, 'crafter_level_ids'):
-      raise _libmod.CrafterLibError('the loaded library has no crafter_level_ids (an older build): level sets are not available')
+    fn = _libmod.require(self._lib, 'crafter_level_ids', 'level sets')
     if out is None:
       out = torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.int32 and
-              tuple(out.shape) == (self.num_envs,) and out.is_contiguous()):
-      raise ValueError(f'out must be a contiguous torch.int32 tensor of shape ({self.num_envs},) on {self.device}')
+    else:
+      self._out(out, (self.num_envs,), torch.int32)
     mask, mptr = self._mask(mask, check_len=True)
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_level_ids(self._handle, mptr, C.c_void_p(out.data_ptr()), self._stream()))
+    self._call(fn, mptr, _ptr(out))
     self._keep = mask
     return out
 
@@ -621,19 +656,12 @@ class BatchedEnv:
     zero-initialised at first use; a step only writes the rows of envs it finished: rows are valid where done != 0.  Everything
     else the call returns and leaves behind is bit-identical to final=False, and the two may be mixed."""
     actions = self._actions(actions)
-    obs, reward, done = self.obs, self.reward, self.done
-    if out is not None:
-      obs = obs if out[0] is None else out[0]
-      reward, done = out[1], out[2]
-      self._check_out(obs, self.obs), self._check_out(reward, self.reward), self._check_out(done, self.done)
+    obs, reward, done = self._step_out(out)
     if final:
       return self._step_final(actions, obs, reward, done, info)
     if self._unbounded:
       self._grow_daylight(1)
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_step(
-          self._handle, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-          C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), self._stream()))
+    self._call(self._lib.crafter_step, _ptr(actions), _ptr(obs), _ptr(reward), _ptr(done))
     self._keep = (actions, obs, reward, done)
     return obs, reward, done, (self.info() if info else {})
 
@@ -647,35 +675,25 @@ class BatchedEnv:
     Host indices (lists, numpy, CPU tensors) are range- and duplicate-checked here and raise ValueError before anything is
     enqueued; a device tensor is checked on the device: a bad list refuses the whole call -- no row changes -- and
     check_errors() raises (ST_BAD_COPY).  out: as for step().  An empty idx enqueues nothing."""
-    if not hasattr(self._lib, 'crafter_step_envs'):
-      raise _libmod.CrafterLibError('the loaded library has no crafter_step_envs (an older build): step_envs is not available')
-    i, hi = self._index(idx, self.num_envs, 'idx')
-    if hi is not None and len(np.unique(hi)) != len(hi):
-      raise ValueError('idx names an env twice')
+    fn = _libmod.require(self._lib, 'crafter_step_envs', 'step_envs')
+    i, _ = self._index(idx, self.num_envs, 'idx', unique=True)
     actions = self._actions(actions).reshape(-1)
     if actions.numel() != i.numel():
       raise ValueError(f'actions has {actions.numel()} entries, idx names {i.numel()} envs')
     if i.numel() > self.num_envs:
       raise ValueError(f'idx names {i.numel()} envs, the batch has {self.num_envs}')
-    obs, reward, done = self.obs, self.reward, self.done
-    if out is not None:
-      obs = obs if out[0] is None else out[0]
-      reward, done = out[1], out[2]
-      self._check_out(obs, self.obs), self._check_out(reward, self.reward), self._check_out(done, self.done)
+    obs, reward, done = self._step_out(out)
     if i.numel():
       if self._unbounded:
         self._grow_daylight(1)
-      with torch.cuda.device(self.device):
-        self._check(self._lib.crafter_step_envs(
-            self._handle, C.c_void_p(i.data_ptr()), int(i.numel()), C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-            C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), self._stream()))
+      self._call(fn, _ptr(i), int(i.numel()), _ptr(actions), _ptr(obs), _ptr(reward), _ptr(done))
       self._keep = (i, actions, obs, reward, done)
     return obs, reward, done, (self.info() if info else {})
 
   def final_buffers(self):
     """The persistent device tensors step(final=True) writes and returns in its info dict: {'final_obs' (absent with
     render=False), 'terminated', 'final_local', 'final_stats'}; allocated at first use, zero-initialised."""
-    if getattr(self, '_final', None) is None:
+    if self._final is None:
       ls, ss = self.symbolic_shape
       n = self.num_envs
       with torch.cuda.device(self.device):
@@ -690,16 +708,12 @@ class BatchedEnv:
   def _step_final(self, actions, obs, reward, done, info):
     if not self.cfg.auto_reset:
       raise ValueError('step(final=True) needs auto_reset=True: without it obs already is the finished episode\'s last frame')
-    if not hasattr(self._lib, 'crafter_step_final'):
-      raise _libmod.CrafterLibError('the loaded library has no crafter_step_final (an older build): step(final=True) is not available')
+    fn = _libmod.require(self._lib, 'crafter_step_final', 'step(final=True)')
     f = self.final_buffers()
     if self._unbounded:
       self._grow_daylight(1)
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_step_final(
-          self._handle, ptr(actions), ptr(obs), ptr(reward), ptr(done), ptr(f['final_obs']) if 'final_obs' in f else None,
-          ptr(f['terminated']), ptr(f['final_local']), ptr(f['final_stats']), self._stream()))
+    self._call(fn, _ptr(actions), _ptr(obs), _ptr(reward), _ptr(done), _ptr(f.get('final_obs')), _ptr(f['terminated']),
+               _ptr(f['final_local']), _ptr(f['final_stats']))
     self._keep = (actions, obs, reward, done)
     out = self.info() if info else {}
     out.update(f)
@@ -715,25 +729,10 @@ class BatchedEnv:
     if actions.dim() != 2 or actions.shape[1] != self.num_envs or actions.shape[0] < 1:
       raise ValueError(f'actions must have shape [T, {self.num_envs}]')
     T = int(actions.shape[0])
-    obs = obs and bool(self.cfg.render_obs)   # render=False: no kernel draws, there is no frame to return (step() hands out zeros)
-    if out is None:
-      o = torch.empty((T,) + tuple(self.obs.shape), dtype=torch.uint8, device=self.device) if obs else None
-      r = torch.empty((T, self.num_envs), dtype=torch.float32, device=self.device)
-      d = torch.empty((T, self.num_envs), dtype=torch.uint8, device=self.device)
-    else:
-      o, r, d = out
-      for t, like in ((o, self.obs), (r, self.reward), (d, self.done)):
-        if t is None and like is self.obs:
-          continue
-        if not (t.is_cuda and t.dtype == like.dtype and tuple(t.shape) == (T,) + tuple(like.shape) and t.is_contiguous() and
-                t.data_ptr() % 16 == 0):
-          raise ValueError(f'out tensor must be a contiguous, 16-byte aligned {like.dtype} device tensor of shape {(T,) + tuple(like.shape)}')
+    o, r, d = self._rollout_out(T, self.num_envs, out, obs)   # (render=False: no frames; step() hands out zeros)
     if self._unbounded:
       self._grow_daylight(T)
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_step_n(
-          self._handle, T, C.c_void_p(actions.data_ptr()), C.c_void_p(o.data_ptr()) if o is not None else None,
-          C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()), self._stream()))
+    self._call(self._lib.crafter_step_n, T, _ptr(actions), _ptr(o), _ptr(r), _ptr(d))
     self._keep = (actions, o, r, d)
     return o, r, d
 
@@ -749,11 +748,8 @@ class BatchedEnv:
     the device -- a bad list refuses the whole call, no state row and no output byte changes, and check_errors() raises
     (ST_BAD_COPY).  out = (obs or None, reward, done): tensors of those shapes to write into.  obs=False, or a batch with
     render=False: no frames.  An empty idx enqueues nothing."""
-    if not hasattr(self._lib, 'crafter_step_n_envs'):
-      raise _libmod.CrafterLibError('the loaded library has no crafter_step_n_envs (an older build): rollout_envs is not available')
-    i, hi = self._index(idx, self.num_envs, 'idx')
-    if hi is not None and len(np.unique(hi)) != len(hi):
-      raise ValueError('idx names an env twice')
+    fn = _libmod.require(self._lib, 'crafter_step_n_envs', 'rollout_envs')
+    i, _ = self._index(idx, self.num_envs, 'idx', unique=True)
     n = int(i.numel())
     if n > self.num_envs:
       raise ValueError(f'idx names {n} envs, the batch has {self.num_envs}')
@@ -763,34 +759,13 @@ class BatchedEnv:
     if actions.dim() != 2 or actions.shape[1] != n or actions.shape[0] < 1:
       raise ValueError(f'actions must have shape [T, {n}] with T >= 1 (idx names {n} envs)')
     T = int(actions.shape[0])
-    obs = obs and bool(self.cfg.render_obs)   # render=False: no kernel draws, there is no frame to return
-    shapes = (((T, n) + tuple(self.obs.shape[1:]), torch.uint8), ((T, n), torch.float32), ((T, n), torch.uint8))
-    if out is None:
-      o, r, d = (torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
-      if not obs:
-        o = None
-    else:
-      o, r, d = out   # (as rollout(): an obs tensor given here is written whatever `obs` says)
-      for t, (shape, dt) in zip((o, r, d), shapes):
-        if t is None and shape is shapes[0][0]:
-          continue
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and
-                t.data_ptr() % 16 == 0):
-          raise ValueError(f'out tensor must be a contiguous, 16-byte aligned {dt} device tensor of shape {shape}')
+    o, r, d = self._rollout_out(T, n, out, obs)
     if n:
       if self._unbounded:
         self._grow_daylight(T)
-      with torch.cuda.device(self.device):
-        self._check(self._lib.crafter_step_n_envs(
-            self._handle, C.c_void_p(i.data_ptr()), n, T, C.c_void_p(actions.data_ptr()), C.c_void_p(o.data_ptr()) if o is not None else None,
-            C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()), self._stream()))
+      self._call(fn, _ptr(i), n, T, _ptr(actions), _ptr(o), _ptr(r), _ptr(d))
       self._keep = (i, actions, o, r, d)
     return o, r, d
-
-  @staticmethod
-  def _check_out(t, like):
-    if not (t.is_cuda and t.dtype == like.dtype and t.shape == like.shape and t.is_contiguous() and t.data_ptr() % 16 == 0):
-      raise ValueError(f'out tensor must be a contiguous, 16-byte aligned {like.dtype} device tensor of shape {tuple(like.shape)}')
 
   def _render_handle(self, size):
     """A second handle with another frame size over the SAME state buffers: Env.render(size)
@@ -816,8 +791,7 @@ class BatchedEnv:
     shape = (self.num_envs, h.cfg.size_h, h.cfg.size_w, 3)
     out = torch.zeros(shape, dtype=torch.uint8, device=self.device) if out is None else out
     mask, mptr = self._mask(mask)
-    with torch.cuda.device(self.device):
-      h.check(self._lib.crafter_render(h.ptr, mptr, C.c_void_p(out.data_ptr()), self._stream()))
+    self._call(self._lib.crafter_render, mptr, _ptr(out), handle=h)
     self._keep = mask
     return out
 
@@ -852,15 +826,11 @@ class BatchedEnv:
     else:
       if len(out) != 2:
         raise ValueError('out must be a pair (local, stats)')
-      for t, (shape, dt) in zip(out, shapes):
-        if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dt and tuple(t.shape) == shape and
-                t.is_contiguous()):
-          raise ValueError(f'out tensor must be a contiguous {dt} tensor of shape {shape} on {self.device}')
+      for k, (t, (shape, dt)) in enumerate(zip(out, shapes)):
+        self._out(t, shape, dt, f'out[{k}]')
     mask, mptr = self._mask(mask, check_len=True)
     local, stats = out
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_symbolic(self._handle, mptr, C.c_void_p(local.data_ptr()), C.c_void_p(stats.data_ptr()),
-                                             self._stream()))
+    self._call(self._lib.crafter_symbolic, mptr, _ptr(local), _ptr(stats))
     self._keep = mask
     return local, stats
 
@@ -881,12 +851,10 @@ class BatchedEnv:
     shape = (self.num_envs, self.num_actions)
     if out is None:
       out = torch.zeros(shape, dtype=torch.uint8, device=self.device)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.uint8 and
-              tuple(out.shape) == shape and out.is_contiguous()):
-      raise ValueError(f'out must be a contiguous torch.uint8 tensor of shape {shape} on {self.device}')
+    else:
+      self._out(out, shape, torch.uint8)
     mask, mptr = self._mask(mask, check_len=True)
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_legal_actions(self._handle, mptr, C.c_void_p(out.data_ptr()), self._stream()))
+    self._call(self._lib.crafter_legal_actions, mptr, _ptr(out))
     self._keep = mask
     return out
 
@@ -908,19 +876,28 @@ class BatchedEnv:
     return out
 
   # ------------------------------------------------------------------ copies of envs
-  def _index(self, idx, rows, what):
-    """-> (contiguous device int32 tensor, host-checked).  Host indices (lists, numpy, CPU tensors) are range-checked here and
-    raise ValueError before anything is enqueued; device tensors are checked by the library on the device (ST_BAD_COPY)."""
-    if torch.is_tensor(idx) and idx.is_cuda:
-      if idx.device != self.device:
-        raise ValueError(f'{what}: index tensor on {idx.device}, batch on {self.device}')
-      return idx.reshape(-1).to(torch.int32).contiguous(), None
+  @staticmethod
+  def _host_index(idx, rows, what, unique=False):
+    """Host indices (a list, a numpy array, a CPU tensor), callable without a device: -> int64 numpy, flat.  ValueError unless
+    they are integers in 0 .. rows - 1 and, with unique, name no row twice."""
     a = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx).reshape(-1)
     if a.size and not np.issubdtype(a.dtype, np.integer):
       raise ValueError(f'{what}: indices must be integers')
     a = a.astype(np.int64)
     if a.size and (a.min() < 0 or a.max() >= rows):
       raise ValueError(f'{what}: index out of range 0 .. {rows - 1}')
+    if unique and len(np.unique(a)) != len(a):
+      raise ValueError(f'{what} names an env twice')
+    return a
+
+  def _index(self, idx, rows, what, unique=False):
+    """-> (contiguous device int32 tensor, the host values or None).  Host indices are checked here (_host_index) and raise
+    ValueError before anything is enqueued; device tensors are not read back: the library checks them on the device (ST_BAD_COPY)."""
+    if _on_device(idx):
+      if idx.device != self.device:
+        raise ValueError(f'{what}: index tensor on {idx.device}, batch on {self.device}')
+      return idx.reshape(-1).to(torch.int32).contiguous(), None
+    a = self._host_index(idx, rows, what, unique)
     return torch.from_numpy(a.astype(np.int32)).to(self.device), a
 
   def _geometry(self):
@@ -935,17 +912,12 @@ class BatchedEnv:
     later episodes included.  Enqueued on the current stream.  A destination named twice or also named as a source is refused:
     host indices raise ValueError, device indices refuse the whole call on the device (check_errors: ST_BAD_COPY)."""
     s, hs = self._index(src, self.num_envs, 'src')
-    d, hd = self._index(dst, self.num_envs, 'dst')
+    d, hd = self._index(dst, self.num_envs, 'dst', unique=True)
     if s.numel() != d.numel():
       raise ValueError('src and dst must have the same length')
-    if hd is not None and len(np.unique(hd)) != len(hd):
-      raise ValueError('dst names an env twice')
     if hs is not None and hd is not None and np.intersect1d(hs, hd).size:
       raise ValueError('an env is both a source and a destination')
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_copy_envs(
-          self._handle, C.c_void_p(s.data_ptr()), C.c_void_p(d.data_ptr()), int(s.numel()), C.c_void_p(self.obs.data_ptr()),
-          C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.done.data_ptr()), self._stream()))
+    self._call(self._lib.crafter_copy_envs, _ptr(s), _ptr(d), int(s.numel()), _ptr(self.obs), _ptr(self.reward), _ptr(self.done))
     self._keep = (s, d)
 
   def save_state(self, idx=None):
@@ -957,11 +929,8 @@ class BatchedEnv:
                      self._geometry(), i)
     t = store.tensors
     ptrs = store._ptrs()
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_save_envs(
-          self._handle, C.c_void_p(i.data_ptr()), rows, C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()),
-          C.c_void_p(self.done.data_ptr()), C.byref(ptrs), rows, store.max_objects, C.c_void_p(t['obs'].data_ptr()),
-          C.c_void_p(t['reward'].data_ptr()), C.c_void_p(t['done'].data_ptr()), self._stream()))
+    self._call(self._lib.crafter_save_envs, _ptr(i), rows, _ptr(self.obs), _ptr(self.reward), _ptr(self.done), C.byref(ptrs), rows,
+               store.max_objects, _ptr(t['obs']), _ptr(t['reward']), _ptr(t['done']))
     self._keep = i
     return store
 
@@ -979,9 +948,7 @@ class BatchedEnv:
       raise ValueError(f'load_state: the store is on {store.device}, the batch on {self.device} (EnvStore.to)')
     if store.max_objects > self.cfg.max_objects:
       self._grow_objects(store.max_objects)
-    d, hd = self._index(store.idx if idx is None else idx, self.num_envs, 'idx')
-    if hd is not None and len(np.unique(hd)) != len(hd):
-      raise ValueError('idx names an env twice')
+    d, _ = self._index(store.idx if idx is None else idx, self.num_envs, 'idx', unique=True)
     r = None
     if rows is not None:
       r, _ = self._index(rows, len(store), 'rows')
@@ -991,12 +958,8 @@ class BatchedEnv:
       raise ValueError('idx is longer than the store')
     t = store.tensors
     ptrs = store._ptrs()
-    with torch.cuda.device(self.device):
-      self._check(self._lib.crafter_load_envs(
-          self._handle, C.byref(ptrs), len(store), store.max_objects, C.c_void_p(t['obs'].data_ptr()),
-          C.c_void_p(t['reward'].data_ptr()), C.c_void_p(t['done'].data_ptr()), None if r is None else C.c_void_p(r.data_ptr()),
-          C.c_void_p(d.data_ptr()), int(d.numel()), C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()),
-          C.c_void_p(self.done.data_ptr()), self._stream()))
+    self._call(self._lib.crafter_load_envs, C.byref(ptrs), len(store), store.max_objects, _ptr(t['obs']), _ptr(t['reward']), _ptr(t['done']),
+               _ptr(r), _ptr(d), int(d.numel()), _ptr(self.obs), _ptr(self.reward), _ptr(self.done))
     self._keep = (store, r, d)
     if self._unbounded:   # a loaded episode may be longer than any this batch ran: the next _grow_daylight reads the counters
       self._step_bound = self.cfg.n_daylight

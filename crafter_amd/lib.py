@@ -7,18 +7,6 @@ from . import abi
 
 LIB_PATH = pathlib.Path(__file__).resolve().parent / '_lib' / 'libcrafter_hip.so'
 
-EXPORTS = [
-    'crafter_struct_sizes', 'crafter_abi_version', 'crafter_create', 'crafter_destroy',
-    'crafter_upload_tables', 'crafter_bind_state', 'crafter_lds_bytes', 'crafter_slot_map_derived', 'crafter_step_instance', 'crafter_reset', 'crafter_step', 'crafter_step_n', 'crafter_debug_dispatch_order', 'crafter_debug_set_dispatch_order',
-    'crafter_render', 'crafter_set_timing', 'crafter_get_timing', 'crafter_pool_status', 'crafter_pool_error',
-    'crafter_last_error', 'crafter_debug_eval', 'crafter_extend_daylight',
-    'crafter_exchange_unique_id', 'crafter_exchange_create', 'crafter_exchange_destroy', 'crafter_step_exchange',
-    'crafter_exchange_wait', 'crafter_exchange_error',
-    'crafter_copy_envs', 'crafter_save_envs', 'crafter_load_envs',
-    'crafter_symbolic', 'crafter_step_final', 'crafter_reseed', 'crafter_legal_actions', 'crafter_step_envs',
-    'crafter_set_levels', 'crafter_level_ids', 'crafter_reset_worlds', 'crafter_step_n_envs',
-]
-
 
 class HostTablesC(C.Structure):
   _fields_ = [
@@ -39,6 +27,56 @@ class CrafterLibError(RuntimeError):
   pass
 
 
+vp, i32, i64, text = C.c_void_p, C.c_int32, C.c_int64, C.c_char_p
+_state = C.POINTER(abi.StatePtrs)
+
+# name -> (restype, argtypes, optional): one row per function include/crafter_hip.h declares, in the header's parameter
+# order (tests/test_host_logic.py holds the table against the header, type class by type class).  optional: an A/B build of
+# an older ABI, named by CRAFTER_HIP_LIB (tools/ab_make.sh), may lack the entry point -- everything else works.
+SIGNATURES = {
+    'crafter_struct_sizes': (None, [C.POINTER(i32)], False),
+    'crafter_abi_version': (i32, [], False),
+    'crafter_create': (i32, [C.POINTER(abi.Config), C.POINTER(vp)], False),
+    'crafter_destroy': (None, [vp], False),
+    'crafter_upload_tables': (i32, [vp, C.POINTER(HostTablesC)], False),
+    'crafter_bind_state': (i32, [vp, _state], False),
+    'crafter_lds_bytes': (i32, [vp], False),
+    'crafter_slot_map_derived': (i32, [vp], False),
+    'crafter_step_instance': (i32, [vp], False),
+    'crafter_reset': (i32, [vp] * 4, False),
+    'crafter_step': (i32, [vp] * 6, False),
+    'crafter_step_n': (i32, [vp, i32] + [vp] * 5, False),
+    'crafter_debug_dispatch_order': (i32, [vp, vp], False),
+    'crafter_debug_set_dispatch_order': (i32, [vp, vp], False),
+    'crafter_render': (i32, [vp] * 4, False),
+    'crafter_set_timing': (i32, [vp, i32], False),
+    'crafter_get_timing': (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)], False),
+    'crafter_pool_status': (i32, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], False),
+    'crafter_pool_error': (text, [vp], False),
+    'crafter_last_error': (text, [vp], False),
+    'crafter_debug_eval': (i32, [i32] + [vp] * 5 + [i64, vp], False),
+    'crafter_extend_daylight': (i32, [vp, vp, i32], True),
+    'crafter_exchange_unique_id': (i32, [vp], True),
+    'crafter_exchange_create': (i32, [vp, i32, i32, i32, C.POINTER(vp)], True),
+    'crafter_exchange_destroy': (None, [vp], True),
+    'crafter_step_exchange': (i32, [vp, vp, i32, vp, vp, vp, i64, i64, i64, i32, vp], True),
+    'crafter_exchange_wait': (i32, [vp, i32, vp], True),
+    'crafter_exchange_error': (text, [vp], True),
+    'crafter_copy_envs': (i32, [vp, vp, vp, i32] + [vp] * 4, True),
+    'crafter_save_envs': (i32, [vp, vp, i32, vp, vp, vp, _state, i32, i32] + [vp] * 4, True),
+    'crafter_load_envs': (i32, [vp, _state, i32, i32] + [vp] * 5 + [i32] + [vp] * 4, True),
+    'crafter_symbolic': (i32, [vp] * 5, True),
+    'crafter_step_final': (i32, [vp] * 10, True),
+    'crafter_reseed': (i32, [vp] * 5, True),
+    'crafter_legal_actions': (i32, [vp] * 4, True),
+    'crafter_step_envs': (i32, [vp, vp, i32] + [vp] * 5, True),
+    'crafter_set_levels': (i32, [vp] * 4 + [i32, C.c_uint64, vp], True),
+    'crafter_level_ids': (i32, [vp] * 4, True),
+    'crafter_reset_worlds': (i32, [vp] * 7 + [i32, i32, vp, vp], True),
+    'crafter_step_n_envs': (i32, [vp, vp, i32, i32] + [vp] * 5, True),
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -49,7 +87,8 @@ def load(path=None):
   if _lib is not None:
     return _lib
   import os
-  path = pathlib.Path(path or os.environ.get('CRAFTER_HIP_LIB') or LIB_PATH)   # env override: A/B builds
+  older = bool(os.environ.get('CRAFTER_HIP_LIB'))   # env override: A/B builds, possibly of an older ABI
+  path = pathlib.Path(path or os.environ.get('CRAFTER_HIP_LIB') or LIB_PATH)
   if not path.exists():
     raise CrafterLibError(
         f'{path} not found: the HIP extension is required (no CPU fallback). '
@@ -58,81 +97,28 @@ def load(path=None):
     lib = C.CDLL(str(path))
   except OSError as e:
     raise CrafterLibError(f'cannot load {path}: {e}') from e
-  missing = [n for n in EXPORTS if not hasattr(lib, n)]
-  if os.environ.get('CRAFTER_HIP_LIB'):   # an A/B build of an older ABI (tools/ab_make.sh): everything but the newer entry points works
-    missing = [n for n in missing if n != 'crafter_extend_daylight' and not n.startswith(('crafter_exchange', 'crafter_step_exchange'))
-               and n not in ('crafter_copy_envs', 'crafter_save_envs', 'crafter_load_envs', 'crafter_symbolic', 'crafter_step_final', 'crafter_reseed',
-                             'crafter_legal_actions', 'crafter_step_envs', 'crafter_set_levels', 'crafter_level_ids', 'crafter_reset_worlds',
-                             'crafter_step_n_envs')]
+  missing = []
+  for name, (restype, argtypes, optional) in SIGNATURES.items():
+    fn = getattr(lib, name, None)
+    if fn is not None:
+      fn.restype, fn.argtypes = restype, argtypes
+    elif not (optional and older):
+      missing.append(name)
   if missing:
     raise CrafterLibError(f'{path} lacks symbols {missing}')
-  vp, i32 = C.c_void_p, C.c_int32
-  lib.crafter_struct_sizes.argtypes = [C.POINTER(i32)]
-  lib.crafter_struct_sizes.restype = None
-  lib.crafter_abi_version.restype = i32
-  lib.crafter_create.argtypes = [C.POINTER(abi.Config), C.POINTER(vp)]
-  lib.crafter_destroy.argtypes = [vp]
-  lib.crafter_destroy.restype = None
-  lib.crafter_upload_tables.argtypes = [vp, C.POINTER(HostTablesC)]
-  lib.crafter_bind_state.argtypes = [vp, C.POINTER(abi.StatePtrs)]
-  if hasattr(lib, 'crafter_extend_daylight'):
-    lib.crafter_extend_daylight.argtypes = [vp, vp, i32]
-  lib.crafter_lds_bytes.argtypes = [vp]
-  lib.crafter_lds_bytes.restype = i32
-  lib.crafter_slot_map_derived.argtypes = [vp]
-  lib.crafter_slot_map_derived.restype = i32
-  lib.crafter_step_instance.argtypes = [vp]
-  lib.crafter_step_instance.restype = i32
-  lib.crafter_reset.argtypes = [vp, vp, vp, vp]
-  lib.crafter_step.argtypes = [vp, vp, vp, vp, vp, vp]
-  lib.crafter_step_n.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-  lib.crafter_debug_dispatch_order.argtypes = [vp, vp]
-  lib.crafter_debug_set_dispatch_order.argtypes = [vp, vp]
-  lib.crafter_render.argtypes = [vp, vp, vp, vp]
-  lib.crafter_set_timing.argtypes = [vp, i32]
-  lib.crafter_get_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
-  lib.crafter_pool_status.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-  lib.crafter_pool_error.argtypes = [vp]
-  lib.crafter_pool_error.restype = C.c_char_p
-  lib.crafter_debug_eval.argtypes = [i32, vp, vp, vp, vp, vp, C.c_int64, vp]
-  lib.crafter_last_error.argtypes = [vp]
-  lib.crafter_last_error.restype = C.c_char_p
-  if hasattr(lib, 'crafter_step_exchange'):
-    lib.crafter_exchange_unique_id.argtypes = [vp]
-    lib.crafter_exchange_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
-    lib.crafter_exchange_destroy.argtypes = [vp]
-    lib.crafter_exchange_destroy.restype = None
-    lib.crafter_step_exchange.argtypes = [vp, vp, i32, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, i32, vp]
-    lib.crafter_exchange_wait.argtypes = [vp, i32, vp]
-    lib.crafter_exchange_error.argtypes = [vp]
-    lib.crafter_exchange_error.restype = C.c_char_p
-  if hasattr(lib, 'crafter_copy_envs'):
-    sp = C.POINTER(abi.StatePtrs)
-    lib.crafter_copy_envs.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.crafter_save_envs.argtypes = [vp, vp, i32, vp, vp, vp, sp, i32, i32, vp, vp, vp, vp]
-    lib.crafter_load_envs.argtypes = [vp, sp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-  if hasattr(lib, 'crafter_symbolic'):
-    lib.crafter_symbolic.argtypes = [vp, vp, vp, vp, vp]
-  if hasattr(lib, 'crafter_step_final'):
-    lib.crafter_step_final.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-  if hasattr(lib, 'crafter_reseed'):
-    lib.crafter_reseed.argtypes = [vp, vp, vp, vp, vp]
-  if hasattr(lib, 'crafter_legal_actions'):
-    lib.crafter_legal_actions.argtypes = [vp, vp, vp, vp]
-  if hasattr(lib, 'crafter_step_envs'):
-    lib.crafter_step_envs.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
-  if hasattr(lib, 'crafter_set_levels'):
-    lib.crafter_set_levels.argtypes = [vp, vp, vp, vp, i32, C.c_uint64, vp]
-    lib.crafter_level_ids.argtypes = [vp, vp, vp, vp]
-  if hasattr(lib, 'crafter_reset_worlds'):
-    lib.crafter_reset_worlds.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
-  if hasattr(lib, 'crafter_step_n_envs'):
-    lib.crafter_step_n_envs.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
   sizes = (i32 * 6)()
   lib.crafter_struct_sizes(sizes)
   abi.check_sizes(list(sizes))
   _lib = lib
   return lib
+
+
+def require(lib, symbol, feature):
+  """-> lib's entry point `symbol`; CrafterLibError if an older build (see `optional` above) lacks it."""
+  fn = getattr(lib, symbol, None)
+  if fn is None:
+    raise CrafterLibError(f'the loaded library has no {symbol} (an older build): {feature} is not available')
+  return fn
 
 
 def last_error(lib, handle):

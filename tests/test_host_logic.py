@@ -341,3 +341,118 @@ def test_daylight_table_grows_ahead_of_the_longest_episode():
     assert env.cfg.n_daylight > int(env._rec_i32.max()) + 5000 + 200000 and len(calls) == 4
   finally:
     torch.cuda.device = orig
+
+
+# ------------------------------------------------------------------ the Python binding (crafter_amd/lib.py, batched.py)
+_C_CLASS = {'int': 'i32', 'int32_t': 'i32', 'uint32_t': 'u32', 'int64_t': 'i64', 'uint64_t': 'u64'}
+_CTYPES_CLASS = {ctypes.c_int: 'i32', ctypes.c_int32: 'i32', ctypes.c_uint32: 'u32', ctypes.c_int64: 'i64', ctypes.c_uint64: 'u64'}
+
+
+def _header_prototypes():
+  """include/crafter_hip.h -> {function: (class of the return value, [class of each parameter])}, whole parameter lists
+  (several span lines); classes: pointer (any pointer or array), i32, u32, i64, u64, none (void), string (const char*)."""
+  text = re.sub(r'/\*.*?\*/', '', (ROOT / 'include' / 'crafter_hip.h').read_text(), flags=re.S)
+
+  def cls(decl, ret=False):
+    decl = decl.strip()
+    if ret and decl == 'void':
+      return 'none'
+    if ret and re.fullmatch(r'const\s+char\s*\*', decl):
+      return 'string'
+    if '*' in decl or '[' in decl:
+      return 'pointer'
+    return _C_CLASS[decl.replace('const ', '').split()[0]]
+
+  protos = {}
+  for ret, name, params in re.findall(r'^((?:const\s+)?\w+\s*\**)\s*(crafter_\w+)\s*\(([^)]*)\)\s*;', text, flags=re.M):
+    params = [] if params.strip() == 'void' else params.split(',')
+    protos[name] = (cls(ret, ret=True), [cls(p) for p in params])
+  return protos
+
+
+def _ctypes_class(t):
+  if t is None:
+    return 'none'
+  if t is ctypes.c_char_p:
+    return 'string'
+  if t is ctypes.c_void_p or issubclass(t, (ctypes._Pointer, ctypes.Array)):
+    return 'pointer'
+  return _CTYPES_CLASS[t]
+
+
+def _signature_mismatches(signatures):
+  protos = _header_prototypes()
+  bad = sorted(set(protos) ^ set(signatures))
+  for name in set(protos) & set(signatures):
+    restype, argtypes, _ = signatures[name]
+    mine = (_ctypes_class(restype), [_ctypes_class(t) for t in argtypes])
+    if mine != protos[name]:
+      bad.append((name, mine, protos[name]))
+  return bad
+
+
+def test_signature_table_matches_the_c_header():
+  """lib.SIGNATURES against every prototype of include/crafter_hip.h: the same set of names, and for each the class of the
+  return value and of every parameter, in order.  (The check itself is checked: a table with one i32 read as a pointer, one
+  parameter short or one name short does not pass.)"""
+  from crafter_amd import lib as hiplib
+  protos = _header_prototypes()
+  assert len(protos) == 40 and protos['crafter_abi_version'] == ('i32', []) and protos['crafter_last_error'] == ('string', ['pointer'])
+  assert protos['crafter_set_levels'] == ('i32', ['pointer'] * 4 + ['i32', 'u64', 'pointer'])   # (a list over two lines)
+  assert protos['crafter_struct_sizes'] == ('none', ['pointer']) and protos['crafter_debug_eval'][1][0] == 'i32'
+  assert _signature_mismatches(hiplib.SIGNATURES) == []
+  assert hiplib.EXPORTS == list(hiplib.SIGNATURES)
+  restype, argtypes, optional = hiplib.SIGNATURES['crafter_step_envs']
+  for wrong in ((restype, [ctypes.c_void_p] * 8, optional), (restype, argtypes[:-1], optional), (None, argtypes, optional)):
+    assert [b[0] for b in _signature_mismatches({**hiplib.SIGNATURES, 'crafter_step_envs': wrong})] == ['crafter_step_envs']
+  assert _signature_mismatches({k: v for k, v in hiplib.SIGNATURES.items() if k != 'crafter_reseed'}) == ['crafter_reseed']
+  # optional: exactly what an older ABI may lack -- the daylight growth, the exchange family and the twelve newer entry points
+  optional = {n for n, s in hiplib.SIGNATURES.items() if s[2]}
+  assert {n for n in optional if 'exchange' in n} == {n for n in hiplib.SIGNATURES if 'exchange' in n} and len(optional) == 1 + 6 + 12
+  assert not optional & {'crafter_create', 'crafter_step', 'crafter_step_n', 'crafter_reset', 'crafter_render', 'crafter_last_error'}
+  so = hiplib.load()   # what load() set is the table
+  for name, (restype, argtypes, _) in hiplib.SIGNATURES.items():
+    assert getattr(so, name).restype is restype and list(getattr(so, name).argtypes) == list(argtypes), name
+
+
+def test_require_names_symbol_and_feature():
+  import types
+  from crafter_amd import lib as hiplib
+  stub = types.SimpleNamespace(crafter_step=len)
+  assert hiplib.require(stub, 'crafter_step', 'stepping') is len
+  with pytest.raises(hiplib.CrafterLibError) as e:
+    hiplib.require(stub, 'crafter_reseed', 'level selection')
+  assert 'crafter_reseed' in str(e.value) and 'level selection' in str(e.value) and 'older build' in str(e.value)
+
+
+def test_host_index_checks_without_a_device():
+  import torch
+  from crafter_amd.batched import BatchedEnv
+  check = BatchedEnv._host_index
+  a = check([], 4, 'idx', unique=True)
+  assert a.dtype == np.int64 and a.size == 0
+  for idx in ([3, 0, 2], torch.tensor([3, 0, 2]), np.array([3, 0, 2], np.int16), np.array([[3], [0], [2]])):
+    a = check(idx, 4, 'idx', unique=True)
+    assert a.dtype == np.int64 and a.tolist() == [3, 0, 2]
+  assert check([1, 1, 3], 4, 'idx').tolist() == [1, 1, 3]   # a source may be copied twice
+  for idx, unique in (([0.0, 1.0], False), ([0, -1], False), ([0, 4], False), ([1, 1, 3], True), (torch.tensor([2, 2]), True),
+                      (torch.tensor([0.5]), False), (np.array([7], np.int16), False)):
+    with pytest.raises(ValueError) as e:
+      check(idx, 4, 'dst', unique=unique)
+    assert 'dst' in str(e.value)
+
+
+def test_episodes_arg_checks_without_a_device():
+  import torch
+  from crafter_amd.batched import BatchedEnv
+  check = BatchedEnv._episodes_arg
+  assert check(None, 4, 'the batch has 4 envs') is None
+  for given, want in ((2, [2, 2, 2, 2]), ([1, 2, 3, BatchedEnv.MAX_EPISODE], [1, 2, 3, 2 ** 31 - 3]), (torch.tensor([4, 3, 2, 1]), [4, 3, 2, 1])):
+    eps = check(given, 4, 'the batch has 4 envs')
+    assert eps.dtype == np.int32 and eps.tolist() == want
+  for episodes in ([1, 2, 3], 0, [1, 1, 0, 1], -1, 2 ** 31 - 2, [1.5, 1, 1, 1], [[1, 2], [3, 4], [5, 6]], 1.0):
+    with pytest.raises(ValueError):
+      check(episodes, 4, 'the table has 4 levels')
+  for episodes in ([1, 2, 3], [[1, 2], [3, 4], [5, 6]]):
+    with pytest.raises(ValueError, match='the table has 4 levels'):
+      check(episodes, 4, 'the table has 4 levels')
