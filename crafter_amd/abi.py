@@ -40,6 +40,14 @@ ALL_STATUS_NAMES[STATUS_BAD_WORLD] = (
     'ST_BAD_WORLD: reset(worlds=...) met a world it had to repair (a material id, an object record or a facing out of range; '
     'the record was skipped / the value replaced) or a world id outside the bank (that env was left as it was)')
 
+# parts of a state fingerprint (crafter_hip_types.h CRAFTER_FP_*): bit p of a part mask, column p of fingerprint_parts()
+FP_PARTS = 7
+FP_MAP, FP_OBJECTS, FP_PLAYER, FP_CLOCK, FP_RNG, FP_CHUNKS, FP_IDENT = (1 << p for p in range(FP_PARTS))
+FP_VISIBLE = FP_MAP | FP_OBJECTS | FP_PLAYER
+FP_DYNAMICS = FP_VISIBLE | FP_CLOCK | FP_RNG | FP_CHUNKS
+FP_ALL = FP_DYNAMICS | FP_IDENT
+FP_NAMES = ('map', 'objects', 'player', 'clock', 'rng', 'chunks', 'ident')
+
 # texture slots of TablePtrs.tex_tile (crafter_hip_types.h CRAFTER_TEX_*)
 TEX_MATERIAL0 = 0
 (TEX_PLAYER_LEFT, TEX_PLAYER_RIGHT, TEX_PLAYER_UP, TEX_PLAYER_DOWN, TEX_PLAYER_SLEEP, TEX_COW,

@@ -858,6 +858,42 @@ class BatchedEnv:
     self._keep = mask
     return out
 
+  # ------------------------------------------------------------------ state fingerprints (include/crafter_hip_fingerprint.h)
+  def _fingerprint(self, parts, mask, key, part_hash):
+    fn = _libmod.require(self._lib, 'crafter_fingerprint', 'fingerprint()')
+    mask, mptr = self._mask(mask, check_len=True)
+    self._call(fn, mptr, int(parts) & 0xFFFFFFFF, _ptr(key), _ptr(part_hash))
+    self._keep = mask
+
+  def fingerprint(self, parts=abi.FP_DYNAMICS, mask=None, out=None):
+    """int64 [N] on the device: each env's 64-bit state key over the parts of the bit mask `parts` (crafter_amd.FP_MAP, FP_OBJECTS,
+    FP_PLAYER, FP_CLOCK, FP_RNG, FP_CHUNKS, FP_IDENT; FP_VISIBLE = map | objects | player, FP_DYNAMICS = all but FP_IDENT,
+    FP_ALL); the tensor carries the 64 bits (`& 0xFFFFFFFFFFFFFFFF` on a Python int gives the unsigned value
+    crafter_amd.fingerprint_host computes).  Two rows have equal keys iff -- up to a 64-bit collision; the hash is not
+    cryptographic -- their canonical states (snapshot(i)) agree on those parts: free slot-table records, holes in the table,
+    derived maps, status bits, the last step's outputs and the world pool do not enter.  Two rows with equal FP_DYNAMICS keys
+    produce identical outputs under any common action sequence until the episode ends (FP_IDENT adds which level comes next).
+    After a step() that auto-reset an env the key is the new episode's first state's.  Read-only: no draw from the envs' RNG, no
+    byte of state changes.  mask: rows with a zero byte are left untouched.  out: a contiguous int64 device tensor of shape
+    [N] to write into.  A `parts` of 0 or with a bit above FP_IDENT raises CrafterDeviceError."""
+    if out is None:
+      out = torch.zeros((self.num_envs,), dtype=torch.int64, device=self.device)
+    else:
+      self._out(out, (self.num_envs,), torch.int64)
+    self._fingerprint(parts, mask, out, None)
+    return out
+
+  def fingerprint_parts(self, mask=None, out=None):
+    """int64 [N, FP_PARTS] on the device: the hash of each part by itself, column p for bit p (map, objects, player, clock, rng,
+    chunks, ident) -- which part of two states differs.  mask, out: as fingerprint()."""
+    shape = (self.num_envs, abi.FP_PARTS)
+    if out is None:
+      out = torch.zeros(shape, dtype=torch.int64, device=self.device)
+    else:
+      self._out(out, shape, torch.int64)
+    self._fingerprint(0, mask, None, out)
+    return out
+
   def info(self):
     """Device-tensor views of what the reference puts into ``info`` (env.py:108-115)."""
     o, r = self._off, self._rec_i32

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/crafter_hip.h"
+#include "../../include/crafter_hip_fingerprint.h"
 #include "crafter_rollout.hpp"
 #include "crafter_rollout_subset.hpp"
 #include "crafter_subset.hpp"
@@ -27,6 +28,7 @@
 #include "env_kernels.hpp"
 #include "env_levels.hpp"
 #include "env_worlds.hpp"
+#include "fingerprint.hpp"
 #include "launch_plan.hpp"
 #include "legal.hpp"
 #include "symbolic.hpp"
@@ -902,6 +904,20 @@ int crafter_legal_actions(crafter_handle* h, const uint8_t* mask, uint8_t* legal
   else
     hipLaunchKernelGGL(crafter_legal_actions_kernel<1>, grid, block, 0, s, h->cfg, h->tb, h->st, mask, legal);
   return launched(h, "crafter_legal_actions launch");
+}
+
+// The state fingerprints of the envs as they stand on `stream` (fingerprint.hpp).  Like crafter_symbolic it reads live rows only
+// and waits for no batch of the pool.
+int crafter_fingerprint(crafter_handle* h, const uint8_t* mask, uint32_t parts, uint64_t* key, uint64_t* part_hash, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  if (ready(h, "crafter_fingerprint")) return 1;
+  if (!key && !part_hash) return fail(h, "crafter_fingerprint: both outputs are null");
+  if (parts & ~(uint32_t)CRAFTER_FP_ALL) return fail(h, "crafter_fingerprint: parts names a bit above CRAFTER_FP_IDENT");
+  if (key && !parts) return fail(h, "crafter_fingerprint: a key of no part (parts == 0)");
+  if (adopt_stream(h, s)) return 1;
+  const dim3 grid((unsigned)((h->cfg.num_envs + kFingerprintEnvs - 1) / kFingerprintEnvs)), block(kFingerprintThreads);
+  hipLaunchKernelGGL(crafter_fingerprint_kernel, grid, block, 0, s, h->cfg, h->tb, h->st, mask, parts, key, part_hash);
+  return launched(h, "crafter_fingerprint launch");
 }
 
 #ifdef CRAFTER_PROBES

@@ -369,6 +369,17 @@ crafter_legal_actions_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8
   legal_body<WL, MAP>(w, (int)blockIdx.x * kLegalEnvs + wave, cfg, tb, st, mask, legal);
 }
 
+// crafter_fingerprint (fingerprint.hpp): one wave per env, kFingerprintEnvs envs per workgroup, no LDS and no barrier: the waves
+// of the batch tail and of masked rows leave at once.  One instance: the objects are read from the slot table wherever the maps live.
+__global__ void __launch_bounds__(kFingerprintThreads)
+crafter_fingerprint_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, uint32_t parts,
+                           uint64_t* __restrict__ key, uint64_t* __restrict__ part_hash) {
+  typedef WaveGfx950<kFingerprintThreads> WF;
+  WF w;
+  const int wave = WF::uni((int)(threadIdx.x >> 6));
+  fingerprint_body<WF>(w, (int)blockIdx.x * kFingerprintEnvs + wave, cfg, tb, st, mask, parts, key, part_hash);
+}
+
 // crafter_reseed (env_levels.hpp): one thread per env edits its record and empties its two pool entries.
 __global__ void __launch_bounds__(kReseedThreads)
 crafter_reseed_kernel(Config cfg, StatePtrs st, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_lane,

@@ -38,14 +38,19 @@ struct LevelTable {
   uint32_t cum[kMaxLevels];      // non-decreasing; cum[n - 1] counts as 2^32 whatever it holds
 };
 
-// pick(lane, k): the table entry of the reset that takes an env of draw lane `lane` into its k-th episode.  Counter based
-// (splitmix64's finaliser over lane + golden * k + key); crafter_amd.levels_pick is its numpy mirror.  t->n >= 1.
-__device__ __forceinline__ int level_pick(const LevelTable* t, uint64_t lane, int k) {
-  uint64_t z = lane + 0x9E3779B97F4A7C15ull * (uint64_t)k + t->key;
+// splitmix64's finaliser and its golden-ratio increment: what `pick` below and the state fingerprints (fingerprint.hpp) mix
+// with; crafter_amd.state.mix64 is the numpy mirror.
+constexpr uint64_t kGolden64 = 0x9E3779B97F4A7C15ull;
+__host__ __device__ constexpr uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  const uint64_t u = z >> 32;
+  return z ^ (z >> 31);
+}
+
+// pick(lane, k): the table entry of the reset that takes an env of draw lane `lane` into its k-th episode.  Counter based
+// (mix64 over lane + golden * k + key); crafter_amd.levels_pick is its numpy mirror.  t->n >= 1.
+__device__ __forceinline__ int level_pick(const LevelTable* t, uint64_t lane, int k) {
+  const uint64_t u = mix64(lane + kGolden64 * (uint64_t)k + t->key) >> 32;
   const int n = t->n;
   if (!t->weighted) return (int)((u * (uint64_t)n) >> 32);
   int lo = 0, hi = n - 1;   // first j with cum[j] > u; the last entry takes what is left (at most 16 rounds)

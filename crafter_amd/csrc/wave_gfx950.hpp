@@ -350,6 +350,26 @@ struct WaveGfx950 {
       lv[R0 + k] = i < n ? (uint32_t)map(v[k], i) : beyond;
     }
   }
+  // 4 K registers R0 .. R0 + 4 K - 1: registers R0 + 4 k .. R0 + 4 k + 3 of a lane = the 16-byte record rec[i], i = base + 64 k + lane.
+  // As lane_gather_map: the K loads (one dwordx4 each) are UNPREDICATED (indices clamped to n - 1, n >= 1) and all issued before
+  // the first use.  A lane whose index is beyond n - 1 gets zeros.
+  template <int R0, int K, class T>
+  __device__ __forceinline__ void lane_gather4(int base, int n, const T* rec) {
+    static_assert(sizeof(T) == 16 && alignof(T) == 16, "16-byte records");
+    typedef uint32_t v4 __attribute__((vector_size(16)));
+    v4 v[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      int i = base + 64 * k + (int)lane();
+      v[k] = *(const v4*)(rec + (i < n ? i : n - 1));
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      int i = base + 64 * k + (int)lane();
+#pragma unroll
+      for (int j = 0; j < 4; j++) lv[R0 + 4 * k + j] = i < n ? v[k][j] : 0u;
+    }
+  }
   // two registers at once: f returns 64 bits, the low half goes to slot_lo, the high half to slot_hi
   template <class F>
   __device__ __forceinline__ void lane_set2(int slot_lo, int slot_hi, int base, int n, F f) {
@@ -383,6 +403,16 @@ struct WaveGfx950 {
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
   }
   __device__ __forceinline__ uint32_t lane_read(int slot, int l) const { return __builtin_amdgcn_readlane(lv[slot], l); }  // uniform l
+  // the sum (mod 2^64) of v over the 64 lanes, in every lane: six butterfly rounds through the LDS crossbar, every lane active
+  __device__ __forceinline__ static uint64_t sum64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 63) ^ d) << 2), (int)(uint32_t)v);
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 63) ^ d) << 2), (int)(uint32_t)(v >> 32));
+      v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+  }
 
   // Occupancy registers (env_core.hpp, LaneSlots): lane l of group g holds the packed position x | y << 16 of object slot
   // 64 g + l, 0xFFFFFFFF when the slot holds nothing.  "Which object stands on this cell" is then a compare + ballot over

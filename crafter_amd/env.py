@@ -12,7 +12,7 @@ import collections
 import numpy as np
 import torch
 
-from . import batched, tables, worlds as _worlds
+from . import abi, batched, tables, worlds as _worlds
 
 try:  # gym is optional in the reference too (env.py:11-22)
   import gym
@@ -216,3 +216,7 @@ class Env(BaseClass):
   def legal_actions(self):
     """BatchedEnv.legal_actions() for this env: bool [n_actions], True where the action passes its guards in the current state."""
     return self._batch.legal_actions()[0].cpu().numpy().astype(bool)
+
+  def fingerprint(self, parts=abi.FP_DYNAMICS):
+    """BatchedEnv.fingerprint(parts) for this env: the key as an unsigned Python int."""
+    return int(self._batch.fingerprint(parts)[0].item()) & 0xFFFFFFFFFFFFFFFF

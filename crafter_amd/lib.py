@@ -77,6 +77,12 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 
+# name -> (the header under include/ that declares it, restype, argtypes): entry points that extend the boundary from a header
+# of their own, looked up by name.  Always optional: a library without one loads, and require() says what is missing.
+EXTENSIONS = {
+    'crafter_fingerprint': ('crafter_hip_fingerprint.h', i32, [vp, vp, C.c_uint32, vp, vp, vp]),
+}
+
 _lib = None
 
 
@@ -106,6 +112,10 @@ def load(path=None):
       missing.append(name)
   if missing:
     raise CrafterLibError(f'{path} lacks symbols {missing}')
+  for name, (_, restype, argtypes) in EXTENSIONS.items():
+    fn = getattr(lib, name, None)
+    if fn is not None:
+      fn.restype, fn.argtypes = restype, argtypes
   sizes = (i32 * 6)()
   lib.crafter_struct_sizes(sizes)
   abi.check_sizes(list(sizes))

@@ -83,6 +83,18 @@ def _u64(values):
   return np.array(flat, dtype=np.uint64).reshape(np.shape(values))
 
 
+GOLDEN64 = np.uint64(0x9E3779B97F4A7C15)
+
+
+def mix64(z):
+  """splitmix64's finaliser over a uint64 array (csrc/env_levels.hpp mix64), mod 2^64."""
+  with np.errstate(over='ignore'):
+    z = np.asarray(z, np.uint64)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
 def levels_pick(lanes, k, K, cum=None, key=0):
   """The numpy mirror of the device's `pick` (include/crafter_hip.h crafter_set_levels): the index of the level-table entry an
   env of draw lane `lanes` plays in its k-th episode, under a table of K entries, cumulative weights `cum` (uint32 [K], None:
@@ -93,11 +105,7 @@ def levels_pick(lanes, k, K, cum=None, key=0):
     raise ValueError(f'K must lie in 1 .. {MAX_LEVELS}')
   lanes, k = np.broadcast_arrays(_u64(lanes), np.asarray(k, dtype=np.int64).astype(np.uint64))
   with np.errstate(over='ignore'):
-    z = lanes + np.uint64(0x9E3779B97F4A7C15) * k + np.uint64(int(key) & 0xFFFFFFFFFFFFFFFF)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    z = z ^ (z >> np.uint64(31))
-    u = z >> np.uint64(32)
+    u = mix64(lanes + GOLDEN64 * k + np.uint64(int(key) & 0xFFFFFFFFFFFFFFFF)) >> np.uint64(32)
     if cum is None:
       return ((u * np.uint64(K)) >> np.uint64(32)).astype(np.int32)
   cum = np.asarray(cum)
@@ -105,6 +113,53 @@ def levels_pick(lanes, k, K, cum=None, key=0):
     raise ValueError(f'cum must have shape ({K},)')
   # first j with cum[j] > u; cum[K - 1] counts as 2^32 whatever it holds
   return np.minimum(np.searchsorted(cum[:K - 1].astype(np.uint64), u, side='right'), K - 1).astype(np.int32)
+
+
+def fingerprint_units(snapshot, seed_lane):
+  """The canonical unit sequences a state fingerprint hashes (include/crafter_hip_fingerprint.h): a list of FP_PARTS
+  uint64 arrays -- map, objects, player, clock, rng, chunks, ident -- from a snapshot() dict (BatchedEnv's or OracleEnv's) and
+  the env's seed lane (seed_lanes)."""
+  u32 = lambda values: (np.asarray(values, np.int64) & 0xFFFFFFFF).astype(np.uint64).reshape(-1)
+  mat = np.ascontiguousarray(snapshot['mat'], np.uint8)
+  H = mat.shape[1]
+  cells = mat.reshape(-1)
+  padded = np.zeros((cells.size + 7) // 8 * 8, np.uint8)
+  padded[:cells.size] = cells
+  objects = np.zeros((len(snapshot['objects']), 2), np.uint64)
+  for k, (tp, x, y, health, fx, fy, aux) in enumerate(snapshot['objects']):
+    objects[k, 0] = int(tp) | (int(health) & 0xFF) << 8 | (int(fx) & 0xFF) << 16 | (int(fy) & 0xFF) << 24 | int(x) << 32 | int(y) << 48
+    objects[k, 1] = int(aux) & 0xFFFFFFFF
+  player = list(snapshot['inventory']) + list(snapshot['achievements']) + [int(bool(snapshot['sleeping']))] + [
+      snapshot[k] for k in ('hunger2', 'thirst2', 'fatigue2', 'recover2', 'player_last_health')]
+  mt = np.asarray(snapshot['mt_key'], np.uint32).astype(np.uint64)
+  nchunk_y = (H + abi.CHUNK - 1) // abi.CHUNK
+  chunks = [xmin // abi.CHUNK * nchunk_y + ymin // abi.CHUNK for xmin, _, ymin, _ in snapshot['chunk_order']]
+  return [padded.view('<u8').astype(np.uint64), objects.reshape(-1), u32(player), u32([snapshot['step']]),
+          np.concatenate([mt[0::2] | mt[1::2] << np.uint64(32), u32([snapshot['mt_pos']])]), u32(chunks),
+          np.concatenate([_u64([int(seed_lane)]), u32([snapshot['episode']])])]
+
+
+def fingerprint_combine(part_hashes, parts):
+  """K(parts) from the FP_PARTS part hashes of one env (a row of fingerprint_parts(), as ints of either sign) -> unsigned int."""
+  parts = int(parts)
+  if not 0 < parts <= abi.FP_ALL:
+    raise ValueError(f'parts must be a non-empty mask of bits 0 .. {abi.FP_PARTS - 1}')
+  total = sum(int(h) for p, h in enumerate(part_hashes) if parts >> p & 1) & 0xFFFFFFFFFFFFFFFF
+  with np.errstate(over='ignore'):
+    return int(mix64(np.uint64(parts) * GOLDEN64 + np.uint64(total)))
+
+
+def fingerprint_host(snapshot, seed_lane, parts=abi.FP_ALL):
+  """The numpy mirror of the device's state fingerprint (include/crafter_hip_fingerprint.h), from a snapshot() dict
+  -- BatchedEnv.snapshot(i) or OracleEnv.snapshot() -- and the env's seed lane -> (key over the part mask `parts`, the
+  FP_PARTS part hashes), unsigned Python ints.  Exact: the device computes the same integers."""
+  hashes = []
+  with np.errstate(over='ignore'):
+    for p, units in enumerate(fingerprint_units(snapshot, seed_lane)):
+      salt = mix64(np.uint64(p + 1))
+      terms = mix64((units ^ salt) + np.arange(1, units.size + 1, dtype=np.uint64) * GOLDEN64)
+      hashes.append(int(mix64(salt + np.uint64(units.size) + terms.sum(dtype=np.uint64))))
+  return fingerprint_combine(hashes, parts), hashes
 
 
 def levels_cum(weights):

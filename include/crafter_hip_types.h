@@ -43,6 +43,13 @@ enum { CRAFTER_A_NOOP = 0, CRAFTER_A_MOVE = 1, CRAFTER_A_DO = 2, CRAFTER_A_SLEEP
 enum { CRAFTER_ST_OBJ_OVERFLOW = 1, CRAFTER_ST_BAD_ACTION = 2, CRAFTER_ST_STEP_OVERFLOW = 4, CRAFTER_ST_CHUNK_OVERFLOW = 8,
        CRAFTER_ST_POOL_MISMATCH = 16, CRAFTER_ST_PIPE_STALL = 32,
        CRAFTER_ST_BAD_COPY = 64 };
+/* the parts of a state fingerprint (crafter_hip_fingerprint.h): bit p of a part mask is part p, and part p's hash is
+ * column p of part_hash.  VISIBLE: what a frame depicts; DYNAMICS: every part but IDENT -- two envs with equal DYNAMICS keys
+ * are meant to produce identical outputs under any common action sequence until the episode ends */
+#define CRAFTER_FP_PARTS 7
+enum { CRAFTER_FP_MAP = 1, CRAFTER_FP_OBJECTS = 2, CRAFTER_FP_PLAYER = 4, CRAFTER_FP_CLOCK = 8, CRAFTER_FP_RNG = 16,
+       CRAFTER_FP_CHUNKS = 32, CRAFTER_FP_IDENT = 64,
+       CRAFTER_FP_VISIBLE = 1 | 2 | 4, CRAFTER_FP_DYNAMICS = 63, CRAFTER_FP_ALL = 127 };
 /* texture slots of crafter_host_tables.tex_tile: material id m at CRAFTER_TEX_MATERIAL0 + m (0 = None -> 'unknown'), then
  * the sprites */
 enum { CRAFTER_TEX_MATERIAL0 = 0, CRAFTER_TEX_PLAYER_LEFT = 17, CRAFTER_TEX_PLAYER_RIGHT, CRAFTER_TEX_PLAYER_UP,
