@@ -921,7 +921,7 @@ int crafter_fingerprint(crafter_handle* h, const uint8_t* mask, uint32_t parts, 
 }
 
 #ifdef CRAFTER_PROBES
-// probe builds: the generation kernels' phase clocks (env_kernels.hpp g_gen_probe), read and cleared; synchronises the device
+// probe builds: the generation kernels' phase clocks (gen_bodies.hpp g_gen_probe), read and cleared; synchronises the device
 int crafter_debug_gen_probe(uint64_t out[32]) {
   if (hipDeviceSynchronize() != hipSuccess) return 1;
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gen_probe), 32 * sizeof(uint64_t)) != hipSuccess) return 1;

@@ -1,5 +1,5 @@
 // The kernels of crafter_step_n (open-loop rollouts): see crafter_rollout.hpp for why they are a translation unit of
-// their own, env_kernels.hpp rollout_body / requeue_rollout_body for what they do.
+// their own, step_body.hpp rollout_body / reset_bodies.hpp requeue_rollout_body for what they do.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 

@@ -69,7 +69,7 @@ __device__ __forceinline__ T* rebase_row(T* base, int row, int env, size_t elems
   return (T*)((uintptr_t)base + (uintptr_t)((ptrdiff_t)(row - env) * (ptrdiff_t)(elems * sizeof(T))));
 }
 
-// rollout_body (env_kernels.hpp) for the call's row-th env: the state staged once, resident over the T steps, the next action
+// rollout_body (step_body.hpp) for the call's row-th env: the state staged once, resident over the T steps, the next action
 // fetched a step ahead, the env handed to the regeneration kernel when it stops for want of a world.  The one difference is
 // where a step's outputs go: row t * n + row of the compact arrays.
 template <class W, int LM, int RUL, class S>
@@ -101,7 +101,7 @@ __device__ __forceinline__ void rollout_envs_body(W& w, uint8_t* smem, int env, 
   if (prof && w.leader()) prof[15] = w.clock();
 }
 
-// requeue_rollout_body (env_kernels.hpp) for an env of a subset rollout: stopped at step stalled_at[env]; row: row_of[env].
+// requeue_rollout_body (reset_bodies.hpp) for an env of a subset rollout: stopped at step stalled_at[env]; row: row_of[env].
 template <class W>
 __device__ __forceinline__ void requeue_rollout_envs_body(W& w, uint8_t* smem, int env, int row, int n, const Config& cfg,
                                                  const TablePtrs& tb, const StatePtrs& st, const int32_t* actions, uint8_t* obs,

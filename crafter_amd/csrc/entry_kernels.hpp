@@ -27,7 +27,7 @@ constexpr int kGenLag = 3;    // the launch stream waits for batch j - kGenLag w
 constexpr int kGenStreams = 2; // batches alternate between side streams, so two can be in flight
 constexpr int kMaxLds = 160 * 1024;
 
-template <int LM, int GEO, int RUL>   // LM 1: maps staged in LDS, 0: large world, maps stay in HBM (env_kernels.hpp bind_lds);
+template <int LM, int GEO, int RUL>   // LM 1: maps staged in LDS, 0: large world, maps stay in HBM (env_stage.hpp bind_lds);
                                      // RUL 1: the uploaded rules equal the compiled-in kDefaultRules (types.hpp)
 #ifndef CRAFTER_BIG_WAVES
 #define CRAFTER_BIG_WAVES 6
@@ -91,7 +91,7 @@ crafter_step_wide_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_
   step_body<WS, 1, 1, uint8_t>(w, smem, (int)blockIdx.x, cfg, tb, st, actions, obs, reward, done, ctl);
 }
 
-// Split step of the default instance (env_kernels.hpp "Split step"): the rule half, one wave per env ...
+// Split step of the default instance (step_body.hpp "Split step"): the rule half, one wave per env ...
 constexpr int kRulesThreads = 64;
 __global__ void __launch_bounds__(kRulesThreads)
 crafter_rules_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ actions,
@@ -218,7 +218,7 @@ crafter_reset_worlds_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_
 }
 
 // World pool generation (side streams): three kernels per batch, each walking the batch's segment of the request queue
-// (env_kernels.hpp gen_seed_body / gen_classify_body / gen_resolve_body).  GEO as for the step kernel.
+// (gen_bodies.hpp gen_seed_body / gen_classify_body / gen_resolve_body).  GEO as for the step kernel.
 template <int GEO>
 __global__ void __launch_bounds__(kGenSeedThreads)
 crafter_gen_seed_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parity, int prio, const LevelTable* __restrict__ levels) {

@@ -7,7 +7,7 @@
 //
 //   author_world   : World.reset + RandomState(world seed) + the player at the centre (exactly what WorldGen::reset_env does
 //                    in front of generate_world), then the authored function -- the map, the records, the inventory
-//   reset_world_body : reset_body (env_kernels.hpp) with author_world where reset_env stands
+//   reset_world_body : reset_body (reset_bodies.hpp: the same reset_skeleton) with author_world where reset_env stands
 //
 // The bank comes from a caller and is never trusted: a value that would index outside a table is repaired or its record is
 // skipped, and the env's sticky ST_BAD_WORLD says so (include/crafter_hip.h lists the cases).  The authored function draws
@@ -175,26 +175,12 @@ __device__ __forceinline__ int reset_world_body(W& w, uint8_t* smem, int env, co
     if (w.leader()) st.rec[env].status |= ST_BAD_WORLD;
     return -1;
   }
-  LdsLayout L = big_reset_layout(cfg);   // (= lds_layout for LDS-resident maps)
-  w.scratch = (uint32_t*)(smem + L.scratch);
-  Env<W, S> e(w, cfg, tb, smem + L.rules);
-  bind_lds<W, -1, S>(e, smem, L, st, env);
-  const bool objs_in_place = L.objs < 0;
-  RenderTarget rt = obs_target<W>(cfg, tb, obs, env);
-  Renderer<W, S> r(e, rt, smem + L.render, (uint32_t*)(smem + L.mtb), L.frame_bytes ? smem + L.frame : nullptr);
-  if (cfg.render_obs != 0 && obs != nullptr) r.preload();   // completes under the barriers below
-  load_env(e, st, env, 0);
-  WorldGen<W, S> wg(e, smem + L.wg);
-  author_world(wg, levels, bank, world);
-  e.recount_space();
-  share_registers(e);
-  if (cfg.want_semantic && st.semantic) write_semantic(e, st.semantic, env);
-  if (L.frame_over_objs) store_objs(e, st, env);   // a night frame's pixel buffer reaches into the slot table
-  w.sync();
-  r.render(cfg.render_obs != 0 && obs != nullptr);   // may recycle the LDS map copies: keep it last
-  w.sync();
-  store_env(e, st, env, !L.frame_over_objs && !objs_in_place);
-  return e.rec->episode;
+  return reset_skeleton<W, S>(w, smem, env, cfg, tb, st, obs, nullptr, [&](Env<W, S>& e, const LdsLayout& L) {
+    WorldGen<W, S> wg(e, smem + L.wg);
+    author_world(wg, levels, bank, world);
+    e.recount_space();
+    share_registers(e);
+  });
 }
 
 }  // namespace crafter

@@ -155,11 +155,11 @@ struct SmallDiv {
   __device__ __forceinline__ int mul(int q) const { return W::mul24(q, d); }
 };
 
-// Frame record of a split step (env_kernels.hpp): everything the frame of one env-step depends on.
+// Frame record of a split step (step_body.hpp): everything the frame of one env-step depends on.
 //   [0, 63) material id per view cell (0xFF: outside the map)   [63] 1: no frame this step (env handed to the regeneration kernel)
 //   [64, 127) sprite texture id per view cell (0xFF: none)      [127] player asleep
 //   [128, 144) inventory   [144, 152) daylight of the step (f64)   [152, 156) step   [156, 160) MT19937 stream position   [160, 164) env
-// Night noise generated ahead of the rules (env_kernels.hpp noise_chain): this many consecutive MT19937 states of the env wait
+// Night noise generated ahead of the rules (env_stage.hpp noise_chain): this many consecutive MT19937 states of the env wait
 // in its global scratch.  12: the rules' own draws may have entered the second state (stream position up to 1247), and
 // 1247 + 2 x 63 x 49 < 12 x 624.
 constexpr int kNoiseStates = 12;
@@ -209,7 +209,7 @@ struct Renderer {
   int32_t* s_item_pos;
   const float* div255;   // TablePtrs.unit255 in global memory (the alpha blend's only division).  Until round 6 a 1 KB LDS copy inside the static
                          // block -- read only by frames that blend per pixel (other image sizes, a view with more sprites than the row table holds):
-                         // the default instance's frames take their sprite rows blended from tables, and its workgroup needed the LDS (env_kernels.hpp lds_layout)
+                         // the default instance's frames take their sprite rows blended from tables, and its workgroup needed the LDS (lds_layout.hpp lds_layout)
   uint32_t* cache;       // LDS [kSpriteRow0 + kSpriteRows][unit_x * unit_y]: the row table (lit by day, raw at night), or null
   uint32_t* mtb;         // LDS [624] second MT19937 state buffer (shared with the worldgen scratch), or null
   uint32_t* pix;         // [local_w * local_h]: a night frame's LocalView pixels in noise-stream order, or null.  LDS -- or, for
@@ -217,10 +217,10 @@ struct Renderer {
                          //   12 KB then do not count against the workgroups per CU of the 86 % of frames that are day frames
   bool pix_global = false;
   const uint32_t* noise_raw = nullptr;   // global [kNoiseStates][624]: the states this frame's noise comes from, generated ahead
-                                         // (env_kernels.hpp noise_chain), or null: noise_pass regenerates them in the frame
+                                         // (env_stage.hpp noise_chain), or null: noise_pass regenerates them in the frame
   int noise_base = 0;                    // index of the noise's first word in them
   uint64_t* prof = nullptr;  // optional shader-clock stamps (slots 7, 8)
-  const uint8_t* frame_cells = nullptr;   // LDS: the frame record of a split step (env_kernels.hpp) -- the cell table's input instead of the maps
+  const uint8_t* frame_cells = nullptr;   // LDS: the frame record of a split step (step_body.hpp) -- the cell table's input instead of the maps
 
   uint8_t* static_base;  // LDS: start of the static block (render_static_bytes)
   // What stage_rows put into the material rows of the row table: the rows LIT for (rows_step, rows_sleeping), or (-1) the raw
@@ -459,7 +459,7 @@ struct Renderer {
     preload_issue(q);
     preload_commit(q);
   }
-  // ... by the waves behind the first one only (resident steps, env_kernels.hpp: the rule wave is already running; nothing
+  // ... by the waves behind the first one only (resident steps, step_body.hpp: the rule wave is already running; nothing
   // reads the block before the frame's own barriers)
   __device__ __forceinline__ void preload_beside(bool rows = true) {
     W& w = e.w;
@@ -1203,7 +1203,7 @@ struct Renderer {
     e.rng_invalidate();
   }
 
-  // Night noise from states generated AHEAD (env_kernels.hpp noise_chain; noise_raw = the env's kNoiseStates consecutive
+  // Night noise from states generated AHEAD (env_stage.hpp noise_chain; noise_raw = the env's kNoiseStates consecutive
   // states in global memory, noise_base = the stream position the rules stopped at, in words from the first state's first
   // word): pixel j takes words noise_base + 2 j and + 2 j + 1 wherever they lie -- no state is regenerated here, so there
   // is no order among the pixels, no epoch and no barrier: every thread lights pixels tid, tid + NT, ... (consecutive lanes:

@@ -25,7 +25,7 @@ __device__ __forceinline__ static void mt_wave_sync() {
 }
 
 // TEE 1: every new word also goes to tee[i] (global memory: the noise look-ahead leaves each regenerated state in the env's
-// scratch, env_kernels.hpp noise_chain -- stores that nothing waits for, instead of a copy pass over the finished state)
+// scratch, env_stage.hpp noise_chain -- stores that nothing waits for, instead of a copy pass over the finished state)
 template <int TEE>
 __device__ __attribute__((noinline)) static void mt_twist_lds_impl(uint32_t* mt, uint32_t* tee) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -178,7 +178,7 @@ __device__ __attribute__((noinline)) static void mt_twist_chain(uint32_t* mt, ui
 // NT = workgroup size, a compile-time constant: with a run-time blockDim the compiler versions every
 // block_for loop (stride-1 special cases) and the step kernel no longer fits the instruction cache.
 // FRESH 1 (rollout kernel): the thread index is read through a member that refresh() makes a new value as far as the
-// optimiser can tell -- see rollout_body (env_kernels.hpp); every other kernel reads the hardware register directly.
+// optimiser can tell -- see rollout_body (step_body.hpp); every other kernel reads the hardware register directly.
 template <int NT, int FRESH = 0, int EARLY = 0>   // EARLY 1: the step kernel instance whose frames start before the rules end (kEarlyFrame)
 struct WaveGfx950 {
   static_assert(NT % 64 == 0 && NT >= 64, "whole waves");   // NT == 64: single-wave workgroups (world-pool seeding / resolution), never renders
@@ -460,7 +460,7 @@ struct WaveGfx950 {
   // Words that CONCURRENT kernels exchange (the world pool's header words: the step kernel on the launch stream, the
   // generation kernels on side streams, on other XCDs): relaxed agent-scope atomics, so that every access is one
   // indivisible access of the whole word at the device's coherence point and never a cached, torn or elided one.
-  // (Leader-only and rare: free.  The protocol on top of them is one writer per word at a time -- env_kernels.hpp.)
+  // (Leader-only and rare: free.  The protocol on top of them is one writer per word at a time -- pool_entry.hpp.)
   template <class T>
   __device__ __forceinline__ static T agent_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   template <class T>

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE -- crafter_step_final on the CPU through WaveHost (see wave_host.hpp): the step bodies as hostsim_step
 // (hostsim.cpp) runs them, but with StepCtl::gen_parity = -1 as crafter_step_final launches them, and behind them the queue walk
-// of crafter_requeue_final_kernel with final_reset_body (csrc/env_kernels.hpp).
+// of crafter_requeue_final_kernel with final_reset_body (csrc/reset_bodies.hpp).
 #include "walks.hpp"
 
 using namespace crafter;

@@ -1,4 +1,4 @@
-"""crafter_step_final without a GPU: final_reset_body (csrc/env_kernels.hpp) through the CPU harness (tests/hostsim/final_host.cpp)
+"""crafter_step_final without a GPU: final_reset_body (csrc/reset_bodies.hpp) through the CPU harness (tests/hostsim/final_host.cpp)
 behind the step bodies run with gen_parity = -1, against the oracle -- terminal frame, terminated, the terminal state's symbolic
 pair, and obs / reward / done of every step --, against the plain step path on a second harness env, and once as a stand-alone
 program built with -fsanitize=address,undefined.  The entry point's declaration and export are checked on the library."""

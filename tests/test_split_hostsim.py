@@ -1,5 +1,5 @@
 """The split step (rule half + frame half with the frame record in between: crafter_rules_kernel / crafter_frame_kernel,
-env_kernels.hpp) against the fused step on the CPU harness of the same kernel bodies: identical observations, rewards, dones
+step_body.hpp) against the fused step on the CPU harness of the same kernel bodies: identical observations, rewards, dones
 and state, with and without the world pool, with and without frames."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: how many step workgroups does a CU hold over a launch?  Needs a PROBE BUILD of the library through
-CRAFTER_HIP_LIB: in step_body (env_kernels.hpp), right after stamp(0),
+CRAFTER_HIP_LIB: in step_body (step_body.hpp), right after stamp(0),
     if (prof && w.leader()) prof[14] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
                                        ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);   // HW_ID | XCC_ID << 32
 (device pass only; not part of the shipped kernel -- the step kernel is sensitive to every extra live value).
