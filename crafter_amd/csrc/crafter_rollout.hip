@@ -13,11 +13,8 @@ namespace crafter {
 namespace {
 
 // T steps of env blockIdx.x in one launch
-// (the default geometry's instances: six waves per SIMD -- 80 VGPRs -- are what their 26.9 KB of LDS allow per CU; left to
-// itself the register allocator takes 83 and loses the sixth workgroup.  The generic instances need what they need.)
-#define CRAFTER_ROLLOUT_BOUNDS __launch_bounds__(kStepThreads, GEO == 1 ? 6 : LM == 0 ? (GEO == 2 ? 6 : 4) : 1)   // (GEO 2: the default view on a world of any size, entry_kernels.hpp)
 template <int LM, int GEO, int RUL>
-__global__ void CRAFTER_ROLLOUT_BOUNDS
+__global__ void __launch_bounds__(kStepThreads, rollout_min_waves(LM, GEO))   // (crafter_rollout.hpp)
 crafter_rollout_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ actions,
                        uint8_t* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done,
                        StepCtl ctl, RolloutArgs ra) {

@@ -17,6 +17,12 @@ constexpr int kRequeueThreads = 256;   // inline regeneration (rare): sized like
                                        // 1024-thread workgroup needs a CU with all registers free, and with the world pool's kernels
                                        // resident next to the step kernel even the EMPTY queue check would wait for one (measured: 32 us / step)
 
+// Waves per SIMD that crafter_rollout_kernel and its subset twin (crafter_rollout_subset.hip) are bounded to, instance by
+// instance.  The default geometry's instances: six waves per SIMD -- 80 VGPRs -- are what their 26.9 KB of LDS allow per CU;
+// left to itself the register allocator takes 83 and loses the sixth workgroup.  GEO 2 (the default view on a world of any
+// size, entry_kernels.hpp) likewise; the generic instances need what they need.
+constexpr int rollout_min_waves(int LM, int GEO) { return GEO == 1 ? 6 : LM == 0 ? (GEO == 2 ? 6 : 4) : 1; }
+
 // A launch with start / stop events attached (timing mode: hipExtLaunchKernelGGL) or a plain one -- the plain launch is
 // the cheaper call on the host, which is what bounds small batches (tools/host_overhead.py).
 #define CRAFTER_LAUNCH(kernel, grid, block, lds, stream, start, stop, ...)                                          \

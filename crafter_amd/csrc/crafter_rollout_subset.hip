@@ -29,7 +29,7 @@ crafter_rollout_envs_check_kernel(RolloutEnvsCheck c) {
 
 // T steps of env idx[blockIdx.x] in one launch: crafter_rollout_kernel's launch bounds (crafter_rollout.hip), instance by instance
 template <int LM, int GEO, int RUL>
-__global__ void __launch_bounds__(kStepThreads, GEO == 1 ? 6 : LM == 0 ? (GEO == 2 ? 6 : 4) : 1)
+__global__ void __launch_bounds__(kStepThreads, rollout_min_waves(LM, GEO))
 crafter_rollout_subset_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ actions,
                               uint8_t* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done,
                               StepCtl ctl, RolloutEnvsArgs ra) {

@@ -28,11 +28,8 @@ crafter_step_envs_check_kernel(SubsetCheck c) {
 }
 
 // Workgroup b steps env idx[b]: crafter_step_kernel's body (entry_kernels.hpp) and launch bounds, instance by instance.
-#ifndef CRAFTER_BIG_WAVES
-#define CRAFTER_BIG_WAVES 6
-#endif
 template <int LM, int GEO, int RUL>
-__global__ void __launch_bounds__(kStepThreads, LM == 0 ? CRAFTER_BIG_WAVES : 1)
+__global__ void __launch_bounds__(kStepThreads, step_min_waves(LM))
 crafter_step_subset_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ idx, const int32_t* __restrict__ verdict,
                            const int32_t* __restrict__ actions, uint8_t* __restrict__ obs, float* __restrict__ reward,
                            uint8_t* __restrict__ done, StepCtl ctl) {

@@ -29,10 +29,7 @@ constexpr int kMaxLds = 160 * 1024;
 
 template <int LM, int GEO, int RUL>   // LM 1: maps staged in LDS, 0: large world, maps stay in HBM (env_stage.hpp bind_lds);
                                      // RUL 1: the uploaded rules equal the compiled-in kDefaultRules (types.hpp)
-#ifndef CRAFTER_BIG_WAVES
-#define CRAFTER_BIG_WAVES 6
-#endif
-__global__ void __launch_bounds__(kStepThreads, LM == 0 ? CRAFTER_BIG_WAVES : 1)   // (maps and slot table in global memory: 19 KB of LDS, registers decide how many share a CU)
+__global__ void __launch_bounds__(kStepThreads, step_min_waves(LM))   // (launch_plan.hpp)
 crafter_step_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ actions,
                     uint8_t* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done,
                     StepCtl ctl) {

@@ -88,10 +88,7 @@ __device__ __forceinline__ void stage_commit(const W& w, const T (&r)[K], T* dst
 template <int K, class W, class T>
 __device__ __forceinline__ void stage_out(const W& w, T* dst, const T* src, int n) {
   if (n <= 0) return;
-#ifndef CRAFTER_STORE_BATCH
-#define CRAFTER_STORE_BATCH 0
-#endif
-  if constexpr (W::kThreads >= 256 && !CRAFTER_STORE_BATCH) {   // wide workgroups: an element or two per thread anyway -- the plain loop (and its registers)
+  if constexpr (W::kThreads >= 256) {   // wide workgroups: an element or two per thread anyway -- the plain loop (and its registers)
     for (int i = w.tid(); i < n; i += w.nthreads()) dst[i] = src[i];
     return;
   }
@@ -157,12 +154,6 @@ template <> struct IsFarSlots<FarSlot> { static constexpr bool value = true; };
 // the slot type of the step / rollout kernels' generic-geometry instances: LM 0 (maps in HBM) = FarSlot
 template <int LM> struct StepSlot { typedef uint16_t type; };
 template <> struct StepSlot<0> { typedef FarSlot type; };
-#ifndef CRAFTER_SPAWN_BATCHED
-#define CRAFTER_SPAWN_BATCHED 0   // 1: Env::apply_hits looks for all spawn cells of a round at once (worlds whose maps stay in global memory; see step_body)
-#endif
-#ifndef CRAFTER_FAR_WINDOW
-#define CRAFTER_FAR_WINDOW 0   // 1: LDS windows of the two maps around the player (measured, round 6: what they save the rules and the cell table they cost the stage-in)
-#endif
 #ifndef CRAFTER_FAR_CACHE
 #define CRAFTER_FAR_CACHE 96
 #endif
@@ -222,8 +213,6 @@ struct Env {
   int win_x0 = 0, win_y0 = 0;   // LaneSlots: map coordinates of the material window's first cell (mat = the window)
   // FarSlot (see there): LDS of the scan -- counters ([0] cache entries in use, [1] live records counted, [2] the player's packed
   // position as staged), index, cache, near bits -- and the wave-uniform registers that go with them
-  uint8_t* wmat = nullptr;      // FarSlot: LDS copies of the two maps' windows around the player (kWinX x kWinY cells at win_x0, win_y0 -- every cell
-  uint16_t* wobj = nullptr;     // the rules of one step and its frame can touch); the maps themselves (`mat`, `objmap`) are the env's in global memory
   uint32_t* nctr = nullptr;
   uint8_t* ndm = nullptr;
   Obj* ncache = nullptr;        // (an entry's `pad` word holds its slot)
@@ -235,9 +224,6 @@ struct Env {
   // LDS per env): counts change by atomic adds that return nothing -- nothing on the rule wave's chain waits for them -- and
   // the one reader, the balance pass, fetches its pairs' entries lane-parallel, 64 pairs per round trip (cen()).
   bool census_global = false;
-  // apply_hits looks for all spawn cells of a round at once (maps in HBM: a memory round trip per hit otherwise); the LDS-map
-  // instances keep the wave-wide scan per hit -- a handful of hits per pass there, and the batched search costs registers
-  bool spawn_batched = false;
 
   __device__ __forceinline__ Env(W& w_, const Config& c, const TablePtrs& t) : w(w_), cfg(c), tb(t), R(*t.rules), RG(*t.rules) {}
   // lds_rules: CRAFTER_RULES_HEAD_BYTES of LDS that load_env stages the rules' head into
@@ -413,9 +399,6 @@ struct Env {
     if constexpr (kLane) {
       if (in_window(x, y)) return mat[widx(x, y)];
       return g_mat[cidx(x, y)];
-    } else if constexpr (kFar) {
-      if (in_window(x, y)) return wmat[widx(x, y)];
-      return mat[cidx(x, y)];
     } else {
       return mat[cidx(x, y)];
     }
@@ -425,11 +408,6 @@ struct Env {
     if constexpr (kLane) {
       int s = w.occ_find((uint32_t)x | ((uint32_t)y << 16), nobj);
       return s < 0 ? 0 : s;
-    } else if constexpr (kFar) {
-      if (W::uni((int)in_window(x, y))) return wobj[widx(x, y)];
-      int far = objmap[cidx(x, y)];
-      W::keep_apart();
-      return far;
     } else {
       return objmap[cidx(x, y)];
     }
@@ -438,18 +416,12 @@ struct Env {
   __device__ __forceinline__ int slot_lane(int x, int y) const {
     if constexpr (kLane) {
       return 0;
-    } else if constexpr (kFar) {
-      if (in_window(x, y)) return wobj[widx(x, y)];
-      return objmap[cidx(x, y)];
     } else {
       return objmap[cidx(x, y)];
     }
   }
-  // FarSlot: a slot-map entry changes -- the map in global memory and, for a cell inside it, the window (leader lane / own lane)
-  __device__ __forceinline__ void far_put_objmap(int x, int y, int slot) {
-    objmap[cidx(x, y)] = (SlotT)slot;
-    if (in_window(x, y)) wobj[widx(x, y)] = (uint16_t)slot;
-  }
+  // FarSlot: a slot-map entry changes in the map in global memory (leader lane / own lane)
+  __device__ __forceinline__ void far_put_objmap(int x, int y, int slot) { objmap[cidx(x, y)] = (SlotT)slot; }
   // mat_at for a WAVE-UNIFORM cell (the serial rule code: every lane asks for the same cell).  LaneSlots: written as
   // mat_at the compiler selects between the window's address and the map's and loads through a generic pointer -- a FLAT
   // instruction on every is_free() of the object loop, waited for on both memory counters; here the all-but-always case
@@ -459,11 +431,6 @@ struct Env {
       if (W::uni((int)in_window(x, y))) return mat[widx(x, y)];
       int far = g_mat[cidx(x, y)];
       W::keep_apart();   // (keeps the two loads in their own blocks: merged they become one flat load)
-      return far;
-    } else if constexpr (kFar) {
-      if (W::uni((int)in_window(x, y))) return wmat[widx(x, y)];
-      int far = mat[cidx(x, y)];
-      W::keep_apart();
       return far;
     } else {
       return mat[cidx(x, y)];
@@ -503,8 +470,7 @@ struct Env {
       if (in_window(x, y)) st(mat + widx(x, y), m);
       st(g_mat + i, m);
     } else if constexpr (kFar) {
-      if (in_window(x, y)) st(wmat + widx(x, y), m);
-      st(mat + i, m);
+      st(mat + i, m);   // (the map itself, in global memory)
     } else {
       st(mat + i, m);
       if (g_mat != mat) st(g_mat + i, m);
@@ -1485,11 +1451,8 @@ struct Env {
       uint64_t open = dmask;
       int total = nobj;
       if constexpr (kFar) {
-        // the table is in global memory: the keys of TEN batches per memory round trip (registers 10 .. 19), matched batch by batch
-#ifndef CRAFTER_FAR_KEYS
-#define CRAFTER_FAR_KEYS 4
-#endif
-        constexpr int K = CRAFTER_FAR_KEYS;
+        // the table is in global memory: the keys of four batches per memory round trip (registers 10 .. 13), matched batch by batch
+        constexpr int K = 4;
         for (int b0 = 0; b0 < total && open; b0 += 64 * K) {
           w.template lane_gather_map<10, K>(
               b0, total, 0xFFFFu, [&](int i) -> uint64_t { return *(const uint64_t*)&objs[i]; },
@@ -1499,15 +1462,9 @@ struct Env {
                 return (uint32_t)(chunk_of((int)((v >> 32) & 0xFFFFu), (int)(v >> 48)) * 3 + col - 2);
               });
           despawn_match<10>(b0, total, open);
-          if constexpr (K > 1) despawn_match<11>(b0 + 64, total, open);
-          if constexpr (K > 2) despawn_match<12>(b0 + 128, total, open);
-          if constexpr (K > 3) despawn_match<13>(b0 + 192, total, open);
-          if constexpr (K > 4) despawn_match<14>(b0 + 256, total, open);
-          if constexpr (K > 5) despawn_match<15>(b0 + 320, total, open);
-          if constexpr (K > 6) despawn_match<16>(b0 + 384, total, open);
-          if constexpr (K > 7) despawn_match<17>(b0 + 448, total, open);
-          if constexpr (K > 8) despawn_match<18>(b0 + 512, total, open);
-          if constexpr (K > 9) despawn_match<19>(b0 + 576, total, open);
+          despawn_match<11>(b0 + 64, total, open);
+          despawn_match<12>(b0 + 128, total, open);
+          despawn_match<13>(b0 + 192, total, open);
         }
       } else
       for (int base = 0; base < total && open; base += 64) {
@@ -1518,20 +1475,7 @@ struct Env {
           int col = creature_col(o.type);
           return col < 0 ? 0xFFFFu : (uint32_t)(chunk_of(o.x, o.y) * 3 + col - 2);
         });
-        uint64_t todo = open;
-        while (todo) {
-          int h = __builtin_ctzll(todo);
-          todo &= todo - 1;
-          uint32_t st5 = w.lane_read(5, h);
-          uint64_t m = w.lane_match(0, base, total, st5 & 0xFFFFu);
-          int cnt = __builtin_popcountll(m), kk = (int)(st5 >> 16);
-          if (kk < cnt) {
-            w.lane_put(6, h, (uint32_t)(base + w.kth_set(m, kk)));
-            open &= ~(1ull << h);
-          } else if (cnt) {
-            w.lane_put(5, h, (st5 & 0xFFFFu) | ((uint32_t)(kk - cnt) << 16));
-          }
-        }
+        despawn_match<0>(base, total, open);
       }
     }
     if constexpr (kFar) {
@@ -1547,118 +1491,41 @@ struct Env {
     }
     BAL_ADD(3)
     Obj p = obj_rd(1);
-    // Spawn cells.  Where the maps are plain arrays (every layout but LaneSlots) and a chunk's rows are whole dwords, ALL
-    // spawn hits of the round look for their cell at once, one lane per hit: two rows of the chunk at a time as dwords
-    // (six loads in flight per lane), the bytes equal to the material counted with integer arithmetic, the drawn index
-    // located -- six memory round trips per ROUND of up to 64 hits, where the wave used to gather and scan one chunk per HIT (a 256x256
-    // world balancing at night: ~100 hits, maps in HBM: 200-380 k clocks per balance step, r4e).  The cells' slot-map
-    // entries are fetched the same way; an entry is only read again, serially, if an earlier hit of this very round
-    // touched that cell.  Registers: 0 = the cell found (x | y << 16), 1 = its slot-map entry, 3 = the cell a hit touched.
-    bool batched = spawn_batched && !kLane && (cfg.H & 3) == 0 && (CHUNK & 3) == 0;
-    if (batched) {
-      const uint8_t* mp = (const uint8_t*)mat;
-      w.lane_set(0, 0, nh, [&](int h, int) -> uint32_t {
-        uint32_t r = w.lane_get(4, h);
-        if (!(r & 0x80000000u)) return 0xFFFFFFFFu;
-        int pidx = (int)(r & 0xFFFFu), want = (int)((r >> 16) & 0xFFu);
-        int j = pidx / 3, k = pidx - 3 * j;
-        int c = chunk_order[j];
-        uint32_t pat = (uint32_t)((k == 1) ? R.mat_path : R.mat_grass) * 0x01010101u;
-        int cx = c / cfg.nchunk_y, cy = c - cx * cfg.nchunk_y;
-        int xmin = cx * CHUNK, ymin = cy * CHUNK;
-        int nx = imin(xmin + CHUNK, cfg.W) - xmin, nd = (imin(ymin + CHUNK, cfg.H) - ymin) >> 2;   // rows, dwords per row
-        uint32_t found = 0xFFFFFFFFu;
-        int acc = 0;
-        constexpr int kRows = 2;   // rows per pass (six dwords in flight per lane; more cost the step kernel its registers)
-#pragma clang loop unroll(disable)
-        for (int x0 = 0; x0 < nx && found == 0xFFFFFFFFu; x0 += kRows) {
-          uint32_t v[kRows][CHUNK / 4];
-#pragma unroll
-          for (int a = 0; a < kRows; a++)
-#pragma unroll
-            for (int d = 0; d < CHUNK / 4; d++)   // clamped, unconditional: all of them in flight together
-              v[a][d] = *(const uint32_t*)(mp + cidx(xmin + imin(x0 + a, nx - 1), ymin) + 4 * imin(d, nd - 1));
-#pragma unroll
-          for (int a = 0; a < kRows; a++)
-#pragma unroll
-            for (int d = 0; d < CHUNK / 4; d++) {
-              if (x0 + a >= nx || d >= nd) continue;
-              uint32_t m = v[a][d] ^ pat;
-              uint32_t z = ~(((m & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | m | 0x7F7F7F7Fu);   // 0x80 in every byte that equals the material (exact)
-              int c4 = __builtin_popcount(z);
-              if (found == 0xFFFFFFFFu && want < acc + c4) {
-                int skip = want - acc;
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                  if ((z >> (8 * q + 7)) & 1u) {
-                    if (skip == 0 && found == 0xFFFFFFFFu) found = (uint32_t)(xmin + x0 + a) | ((uint32_t)(ymin + 4 * d + q) << 16);
-                    skip--;
-                  }
-              }
-              acc += c4;
-            }
-        }
-        return found;
-      });
-      w.lane_set(1, 0, nh, [&](int h, int) -> uint32_t {
-        uint32_t f = w.lane_get(0, h);
-        if (f == 0xFFFFFFFFu) return 0u;
-        return (uint32_t)(int)objmap[cidx((int)(f & 0xFFFFu), (int)(f >> 16))];
-      });
-      w.lane_set(3, 0, nh, [&](int, int) -> uint32_t { return 0xFFFFFFFFu; });
-    }
     BAL_ADD(4)
     for (int h = 0; h < nh; h++) {
       uint32_t r = w.lane_read(4, h);
       int pidx = (int)(r & 0xFFFFu), drawn = (int)((r >> 16) & 0xFFu);
       int j = pidx / 3, k = pidx - 3 * j;
       int c = chunk_order[j];
-      uint64_t before = (1ull << h) - 1ull;
       if (r & 0x80000000u) {   // env.py:165-172
         int span_dist = (k == 0) ? 6 : (k == 1) ? 7 : 5;
         int health = (k == 0) ? 5 : 3;
         int type = (k == 0) ? T_ZOMBIE : (k == 1) ? T_SKELETON : T_COW;
-        int x, y;
-        bool empty;
-        if (batched) {
-          uint32_t f = w.lane_read(0, h);
-          if (f == 0xFFFFFFFFu) continue;  // unreachable: space counts exactly these cells
-          x = (int)(f & 0xFFFFu);
-          y = (int)(f >> 16);
-          // (an earlier hit of this round spawned on, or despawned from, this very cell: the prefetched entry is stale)
-          bool touched = (w.lane_match(3, 0, nh, f) & before) != 0;
-          empty = touched ? slot_at(x, y) == 0 : w.lane_read(1, h) == 0;
-        } else {
-          int material = (k == 1) ? R.mat_path : R.mat_grass;
-          int cx = c / cfg.nchunk_y, cy = c - cx * cfg.nchunk_y;
-          int xmin = cx * CHUNK, ymin = cy * CHUNK;
-          int xmax = imin(xmin + CHUNK, cfg.W), ymax = imin(ymin + CHUNK, cfg.H);
-          int ch = ymax - ymin, ncell = (xmax - xmin) * ch;
-          uint32_t inv_ch = (65536u + (uint32_t)ch - 1u) / (uint32_t)ch;   // q / ch for q < 144 by multiplication
-          int i = drawn;  // i-th material cell in x-major order (env.py:166-170)
-          int found = -1;
-          // the chunk's cells (<= 144) into three lane registers at once (LaneSlots: far chunks come from HBM)
-          w.lane_gather3(ncell, [&](int q) -> uint32_t {
-            int dx = (int)(((uint32_t)q * inv_ch) >> 16);
-            int dy = q - dx * ch;
-            return (uint32_t)mat_at(xmin + dx, ymin + dy);
-          });
-          // (the register is named by a literal in every copy of the loop body: indexed by a run-time value the wave's
-          // register array would be put in scratch memory)
-          scan_cells<0>(0, ncell, material, i, found);
-          scan_cells<1>(64, ncell, material, i, found);
-          scan_cells<3>(128, ncell, material, i, found);
-          if (found < 0) continue;  // unreachable: space counts exactly these cells
-          int dx = (int)(((uint32_t)found * inv_ch) >> 16);
-          x = xmin + dx;
-          y = ymin + found - dx * ch;
-          empty = slot_at(x, y) == 0;
-        }
+        int material = (k == 1) ? R.mat_path : R.mat_grass;
+        int cx = c / cfg.nchunk_y, cy = c - cx * cfg.nchunk_y;
+        int xmin = cx * CHUNK, ymin = cy * CHUNK;
+        int xmax = imin(xmin + CHUNK, cfg.W), ymax = imin(ymin + CHUNK, cfg.H);
+        int ch = ymax - ymin, ncell = (xmax - xmin) * ch;
+        uint32_t inv_ch = (65536u + (uint32_t)ch - 1u) / (uint32_t)ch;   // q / ch for q < 144 by multiplication
+        int i = drawn;  // i-th material cell in x-major order (env.py:166-170)
+        int found = -1;
+        // the chunk's cells (<= 144) into three lane registers at once (LaneSlots: far chunks come from HBM)
+        w.lane_gather3(ncell, [&](int q) -> uint32_t {
+          int dx = (int)(((uint32_t)q * inv_ch) >> 16);
+          int dy = q - dx * ch;
+          return (uint32_t)mat_at(xmin + dx, ymin + dy);
+        });
+        // (the register is named by a literal in every copy of the loop body: indexed by a run-time value the wave's
+        // register array would be put in scratch memory)
+        scan_cells<0>(0, ncell, material, i, found);
+        scan_cells<1>(64, ncell, material, i, found);
+        scan_cells<3>(128, ncell, material, i, found);
+        if (found < 0) continue;  // unreachable: space counts exactly these cells
+        int dx = (int)(((uint32_t)found * inv_ch) >> 16);
+        int x = xmin + dx, y = ymin + found - dx * ch;
+        bool empty = slot_at(x, y) == 0;
         bool away = (iabs(x - (int)p.x) + iabs(y - (int)p.y)) >= span_dist;
-        if (empty && away) {
-          obj_add(type, x, y, health, 0, 0, 0);
-          if (batched) w.lane_put(3, h, (uint32_t)x | ((uint32_t)y << 16));
-        }
+        if (empty && away) obj_add(type, x, y, health, 0, 0, 0);
       } else {                 // env.py:174-179
         int despan_dist = (k == 0) ? 0 : (k == 1) ? 7 : 5;
         int slot = (int)w.lane_read(6, h);
@@ -1677,7 +1544,6 @@ struct Env {
             obj_remove(slot, o);
           else
             obj_remove(slot);
-          if (batched) w.lane_put(3, h, (uint32_t)o.x | ((uint32_t)o.y << 16));
         }
       }
     }

@@ -8,7 +8,7 @@
 // and stores the compact tables (slot table, MT key, scalar record, chunk order) on exit.
 // The text lives in one header per concern; this one includes them all:
 //   lds_layout.hpp    geometry predicates, every LDS layout (sizes and offsets, shared with the host)
-//   env_stage.hpp     bind_lds, load_env / store_env, the windows, share_registers, noise_chain, obs_target, write_semantic
+//   env_stage.hpp     bind_lds, load_env / store_env, the material window, share_registers, noise_chain, obs_target, write_semantic
 //   pool_entry.hpp    the world-pool protocol on the device: gen_wanted ... adopt_world
 //   step_body.hpp     StepCtl, the frame record, frame_body, step_body, rollout_body
 //   reset_bodies.hpp  the reset skeleton and its callers, requeue_rollout_body, render_body, final_reset_body

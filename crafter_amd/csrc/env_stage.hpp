@@ -37,9 +37,6 @@ __device__ __forceinline__ void bind_lds(Env<W, S>& e, uint8_t* smem, const LdsL
     e.ndm = smem + L.far + 16;
     e.ncache = (Obj*)(smem + L.far + 16 + 256);
     e.near_mask = (uint64_t*)(smem + L.far + 16 + 256 + 16 * kFarCache);
-    e.wmat = smem + L.wmat;
-    e.wobj = (uint16_t*)(smem + L.wobj);
-    e.win_x0 = e.win_y0 = -(1 << 20);   // (no window yet: every cell is read from the maps)
   }
   e.mt = (uint32_t*)(smem + L.mt);
   e.rec = (EnvRec*)(smem + L.rec);
@@ -190,68 +187,11 @@ __device__ __forceinline__ void window_commit(Env<W, S>& e, const uint8_t* src, 
   }
 }
 
-// FarSlot: the windows of BOTH maps (material bytes, two-byte slot ids) around the player at (px, py), 8 bytes per load;
-// issued once the player's position is known, committed behind the scan's evaluation (which runs while they are in flight).
-template <class W>
-struct FarWindow {
-  static constexpr int NM = kWinX * (kWinY / 8), NO = kWinX * (kWinY / 4);
-  static constexpr int KM = (NM + W::kThreads - 1) / W::kThreads, KO = (NO + W::kThreads - 1) / W::kThreads;
-  uint64_t m[KM], o[KO];
-};
-template <class W, class S>
-__device__ __forceinline__ bool far_window_ok(const Env<W, S>& e) { return CRAFTER_FAR_WINDOW != 0 && e.cfg.W >= kWinX && e.cfg.H >= kWinY && e.cfg.H % 8 == 0; }
-template <class W, class S>
-__device__ __forceinline__ const uint64_t* far_window_src(const Env<W, S>& e, int j, bool slots) {
-  const int per_row = slots ? kWinY / 4 : kWinY / 8;
-  int row = j / per_row, col = j - row * per_row;
-  size_t cell0 = (size_t)(e.win_x0 + row) * e.cfg.H + e.win_y0;
-  const uint8_t* base = slots ? (const uint8_t*)e.objmap + 2 * cell0 : (const uint8_t*)e.mat + cell0;
-  return (const uint64_t*)(base + 8 * col);
-}
-template <class W, class S>
-__device__ __forceinline__ void far_window_issue(Env<W, S>& e, int px, int py, FarWindow<W>& q) {
-  if (!far_window_ok(e)) return;
-  place_window(e, px, py);
-#pragma unroll
-  for (int k = 0; k < FarWindow<W>::KM; k++) {
-    int j = e.w.tid() + k * e.w.nthreads();
-    q.m[k] = *far_window_src(e, j < FarWindow<W>::NM ? j : FarWindow<W>::NM - 1, false);
-  }
-#pragma unroll
-  for (int k = 0; k < FarWindow<W>::KO; k++) {
-    int j = e.w.tid() + k * e.w.nthreads();
-    q.o[k] = *far_window_src(e, j < FarWindow<W>::NO ? j : FarWindow<W>::NO - 1, true);
-  }
-}
-template <class W, class S>
-__device__ __forceinline__ void far_window_commit(Env<W, S>& e, const FarWindow<W>& q) {
-  if (!far_window_ok(e)) return;
-  uint64_t* lm = (uint64_t*)e.wmat;
-  uint64_t* lo = (uint64_t*)e.wobj;
-  const int nt = e.w.nthreads();
-#pragma unroll
-  for (int k = 0; k < FarWindow<W>::KM; k++) {
-    int j = e.w.tid() + k * nt;
-    if (j < FarWindow<W>::NM) lm[j] = q.m[k];
-  }
-#pragma unroll
-  for (int k = 0; k < FarWindow<W>::KO; k++) {
-    int j = e.w.tid() + k * nt;
-    if (j < FarWindow<W>::NO) lo[j] = q.o[k];
-  }
-  // (narrower workgroups than the registers cover: the CPU harness)
-  for (int j = FarWindow<W>::KM * nt + e.w.tid(); j < FarWindow<W>::NM; j += nt) lm[j] = *far_window_src(e, j, false);
-  for (int j = FarWindow<W>::KO * nt + e.w.tid(); j < FarWindow<W>::NO; j += nt) lo[j] = *far_window_src(e, j, true);
-}
-// the scan's second half, behind the barrier that published the record and the player's position: the windows' loads leave,
-// the scan's batches are evaluated, the windows land in LDS.  Ends on a barrier.
+// the scan's second half, behind the barrier that published the record and the player's position: the scan's batches are
+// evaluated.  Ends on a barrier.
 template <class W, class S>
 __device__ __forceinline__ void far_finish_scan(Env<W, S>& e) {
-  FarWindow<W> fw;
-  const uint32_t pp = e.nctr[2];
-  far_window_issue(e, (int)(pp & 0xFFFFu), (int)(pp >> 16), fw);
   e.far_rounds(e.nobj);
-  far_window_commit(e, fw);
   // (read BETWEEN the scan's two barriers: behind the second one the rule wave is on its way and may touch a new chunk before a
   // slower wave has looked -- that wave would then believe nothing changed and keep its share of the chunk tables to itself)
   e.far_chunks_staged = e.rec->nchunks_seen;

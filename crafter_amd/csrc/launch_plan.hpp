@@ -33,6 +33,13 @@ enum StepInstance {
 #undef CRAFTER_X
 };
 
+// Waves per SIMD that crafter_step_kernel and its subset twin (crafter_subset.hip) are bounded to, instance by instance.  LM 0 --
+// maps and slot table in global memory: 19 KB of LDS, registers decide how many share a CU -- takes CRAFTER_BIG_WAVES.
+#ifndef CRAFTER_BIG_WAVES
+#define CRAFTER_BIG_WAVES 6
+#endif
+constexpr int step_min_waves(int LM) { return LM == 0 ? CRAFTER_BIG_WAVES : 1; }
+
 constexpr int kEarlyMinEnvs = 8 * 256;   // crafter_step_early_kernel from this many envs on (same-box A/B, profiles/r6_early_frame_ab.txt: 1536 envs -1.0 %, 2048 / 3072 +0.3 %, 4096 +0.1 ... +1.0 %, 8192 +1.2 %)
 // crafter_step_wide_kernel for batches of at most two envs per CU (one GPU's share of configs[2]).  Measured
 // (profiles/r4zy_wide_ab.txt): kernel 27.8 -> 26.3 us at 512 envs (+4.8 % env-steps/s), +5 % at 256; at 768 envs -5 %, at

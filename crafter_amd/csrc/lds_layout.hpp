@@ -43,7 +43,6 @@ struct LdsLayout {
   int frame_over_objs = 0;   // the LDS frame extends over the slot table: objs must be stored before the frame is composed
   int mat, objmap, frame, frame_bytes, objs, mt, rec, rules, chunk_order, chunk_seen, census, wg, scratch, render, total;
   int mtb = -1;      // the second MT19937 state (night frames; the worldgen's stream window): inside the wg region
-  int wmat = -1, wobj = -1;   // big_layout: the windows of the two maps around the player (env_core.hpp FarSlot)
   int far = -1;      // big_layout: the scan's counters, index, record cache and near bits (env_core.hpp FarSlot); the slot table itself stays in global memory
   int total_no_render;   // the renderer's region comes last: kernels that never draw (world-pool generation) launch without it
 };
@@ -163,12 +162,6 @@ __host__ __device__ inline LdsLayout big_layout(const Config& c) {
   L.objs = -1;
   L.far = o;          o += far_lds_bytes(c.max_objects);
   L.wg = L.mtb = o;   o += align16(4 * MT_N);   // (no pixel buffer in LDS, no worldgen: of the scratch only the second MT state)
-#if CRAFTER_FAR_WINDOW
-  L.wmat = o;         o += align16(kWinX * kWinY);
-  L.wobj = o;         o += align16(2 * kWinX * kWinY);
-#else
-  L.wmat = L.wobj = o;
-#endif
   layout_tail(L, o, c, CRAFTER_RULES_HEAD_BYTES, false);
   layout_end(L, o, align16(render_lds_bytes(c)));
   return L;

@@ -173,7 +173,6 @@ __device__ __forceinline__ void adopt_world(Env<W, S>& e, const StatePtrs& st, i
     }
     e.far_live = hdr.nobj - 1;
     e.far_chunks_staged = -1;
-    e.win_x0 = e.win_y0 = -(1 << 20);   // (the windows showed the old world: the frame reads the new maps)
     e.cur_slot = -1;
     e.cur_idx = -1;
     W::drain_stores();   // (the table's new records are read straight from the coherence point: Env::obj_rd_lane)

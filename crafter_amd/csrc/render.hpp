@@ -284,6 +284,8 @@ struct Renderer {
   struct Lit {
     double D, iD, hD, amount;   // daylight, 1 - daylight, (1 - daylight) * 0.5, 2 * (0.5 - daylight)
     bool night, sleeping;
+    __device__ __forceinline__ Lit(double daylight, bool asleep)
+        : D(daylight), iD(1 - D), hD(iD * 0.5), amount(2 * (0.5 - D)), night(D < 0.5), sleeping(asleep) {}
   };
 
   // The lit material rows of a day step (render_lit_bytes) sit in global memory (5.6 MB, L2 / MALL resident).  Round 2
@@ -299,6 +301,25 @@ struct Renderer {
   __device__ __forceinline__ const uint32_t* blended_rows() const {
     const Config& c = e.cfg;
     return (const uint32_t*)(e.tb.render_static + render_static_bytes(c) + render_item_cells_bytes(c) + render_lit_bytes(c) + render_night_px_bytes(c));
+  }
+  // the night pixel records (render_night_px_bytes)
+  __device__ __forceinline__ const NightPx* night_px() const {
+    const Config& c = e.cfg;
+    return (const NightPx*)(e.tb.render_static + render_static_bytes(c) + render_item_cells_bytes(c) + render_lit_bytes(c));
+  }
+  // the raw material rows at the static block's end
+  __device__ __forceinline__ const vec16* raw_rows() const {
+    return (const vec16*)(e.tb.render_static + render_static_bytes(e.cfg) - texel_cache_bytes(e.cfg));
+  }
+  // The row table's material rows from `src` (raw_rows(), or a step's lit rows), by the threads of `loop` (consumer_for /
+  // block_for): whole 16-byte units, then the odd words -- not a byte beyond the material rows: the table's sprite rows begin
+  // right behind the last material texel, and they have another writer (build_tables' first wave)
+  template <class Loop>
+  __device__ __forceinline__ void copy_material_rows(const vec16* src, Loop loop) {
+    const int words = kSpriteRow0 * rt.unit_x * rt.unit_y;
+    vec16* dst = (vec16*)cache;
+    loop(words / 4, [&](int i) { dst[i] = src[i]; });
+    loop(words & 3, [&](int i) { cache[(words & ~3) + i] = ((const uint32_t*)src)[(words & ~3) + i]; });
   }
   __device__ __forceinline__ const uint32_t* lit_sprite_rows(int step, bool sleeping) const {
     const Config& c = e.cfg;
@@ -367,13 +388,7 @@ struct Renderer {
       w.block_for(2 * steps * words, [&](int i) {
         int hs = i / words, j = i - hs * words;
         int step = hs < steps ? hs : hs - steps;
-        Lit L;
-        L.D = e.tb.daylight[step];
-        L.iD = 1 - L.D;
-        L.hD = L.iD * 0.5;
-        L.night = L.D < 0.5;
-        L.sleeping = hs >= steps;
-        L.amount = 2 * (0.5 - L.D);
+        Lit L(e.tb.daylight[step], hs >= steps);
         uint32_t tile = j < kSpriteRow0 * rt.unit_x * rt.unit_y ? cache[j] : 0u;   // (behind the last row: padding)
         int v[3] = {(int)(tile & 0xFF), (int)((tile >> 8) & 0xFF), (int)((tile >> 16) & 0xFF)};
         lit[i] = (L.night || j >= kSpriteRow0 * rt.unit_x * rt.unit_y) ? tile : light(v, L, 0.0, 0.0);
@@ -421,13 +436,7 @@ struct Renderer {
     uint32_t* lit = (uint32_t*)bl + words;
     for (int hs = part; hs < 2 * steps; hs += nparts) {
       int step = hs < steps ? hs : hs - steps;
-      Lit L;
-      L.D = e.tb.daylight[step];
-      L.iD = 1 - L.D;
-      L.hD = L.iD * 0.5;
-      L.night = L.D < 0.5;
-      L.sleeping = hs >= steps;
-      L.amount = 2 * (0.5 - L.D);
+      Lit L(e.tb.daylight[step], hs >= steps);
       uint32_t* out = lit + (size_t)hs * words;
       w.block_for(words, [&](int j) {
         uint32_t tile = bl[j];
@@ -487,13 +496,125 @@ struct Renderer {
     W& w = e.w;
     if (!cache) return;
     const bool lit = daylight >= 0.5 && step < render_lit_steps(c);
-    const vec16* src = lit ? (const vec16*)lit_rows(step, sleeping) : (const vec16*)(e.tb.render_static + render_static_bytes(c) - texel_cache_bytes(c));
-    // (whole 16-byte units, then the odd words: the row table's sprite rows begin right behind the last material texel, and
-    // they have another writer -- build_tables)
-    const int words = kSpriteRow0 * rt.unit_x * rt.unit_y;
-    vec16* dst = (vec16*)cache;
-    w.consumer_for(words / 4, [&](int i) { dst[i] = src[i]; });
-    w.consumer_for(words & 3, [&](int i) { cache[(words & ~3) + i] = ((const uint32_t*)src)[(words & ~3) + i]; });
+    copy_material_rows(lit ? (const vec16*)lit_rows(step, sleeping) : raw_rows(), [&](int n, auto f) { w.consumer_for(n, f); });
+  }
+
+  // ---- Quad mode's pieces, shared by early_frame / finish_frame / render: every quad of four output pixels is owned by one thread.
+  // four pixels (packed 0x..BBGGRR, the top byte ignored) as the 12 bytes of quad g of output row y
+  struct Px4 { uint32_t a, b, c; };
+  __device__ __forceinline__ void store_quad(int y, int g, const uint32_t (&px)[4]) const {
+    const uint32_t p0 = px[0] & 0xFFFFFFu, p1 = px[1] & 0xFFFFFFu, p2 = px[2] & 0xFFFFFFu, p3 = px[3] & 0xFFFFFFu;
+    Px4 v = {p0 | (p1 << 24), (p1 >> 8) | (p2 << 16), (p2 >> 16) | (p3 << 8)};
+    *(Px4*)(rt.out + W::mul24(y, 3 * rt.size_w) + 12 * g) = v;
+  }
+  // what is left of the canvas below the inventory strip is zeros (env.py:123): tail_quads quads from row y0 on
+  __device__ __forceinline__ void zero_tail(int tid, int y0, int tail_quads) const {
+    for (int gi = tid; gi < tail_quads; gi += W::kThreads) {
+      Px4 v = {0u, 0u, 0u};
+      *(Px4*)(rt.out + W::mul24(y0, 3 * rt.size_w) + 12 * gi) = v;
+    }
+  }
+  // The LocalView quads of thread t: column group g = t % gpr, rows yy[r] = t / gpr + r * rows_per (r < KR).  fetch(g, in, cm, yy, px)
+  // brings their pixels (in[k]: pixel 4 g + k is inside the view, cm[k]: its colmap entry; loads clamped instead of predicated);
+  // beyond the view the canvas stays untouched, and only the store is guarded.
+  template <int KR, class Fetch>
+  __device__ __forceinline__ void local_quads(int t, int rows_per, const SmallDiv<W>& by_gpr, Fetch fetch) const {
+    const int lw = e.cfg.local_gw * rt.unit_x, lh = e.cfg.local_gh * rt.unit_y;
+    int y0 = by_gpr.div(t), g = t - by_gpr.mul(y0);
+    int cm[4];
+    bool in[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      int x = 4 * g + k;
+      in[k] = x < lw;
+      cm[k] = colmap[in[k] ? x : lw - 1];
+    }
+    int yy[KR];
+    uint32_t px[KR][4];
+#pragma unroll
+    for (int r = 0; r < KR; r++) yy[r] = y0 + r * rows_per;
+    fetch(g, in, cm, yy, px);
+#pragma unroll
+    for (int r = 0; r < KR; r++) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) px[r][k] = in[k] ? px[r][k] : 0u;
+      if (yy[r] < lh) store_quad(yy[r], g, px[r]);
+    }
+  }
+  // ... of a DAY frame, straight from the row table: stage by stage over the thread's rows -- row map, cell rows, texels -- up
+  // to 4 KR independent chains in flight
+  template <int KR>
+  __device__ __forceinline__ void day_rows(const int (&cm)[4], const int (&yy)[KR], uint32_t (&px)[KR][4]) const {
+    const Config& c = e.cfg;
+    const int lh = c.local_gh * rt.unit_y, ntex = rt.unit_x * rt.unit_y;
+    int rbase[KR], ty[KR], row[KR][4];
+#pragma unroll
+    for (int r = 0; r < KR; r++) {
+      int rm = rowmap[yy[r] < lh ? yy[r] : lh - 1];
+      rbase[r] = rm & 0xFF;
+      ty[r] = rm >> 8;
+    }
+#pragma unroll
+    for (int r = 0; r < KR; r++)
+#pragma unroll
+      for (int k = 0; k < 4; k++) row[r][k] = cell_row[W::mul24(cm[k] & 0xFF, c.local_gh) + rbase[r]];
+#pragma unroll
+    for (int r = 0; r < KR; r++)
+#pragma unroll
+      for (int k = 0; k < 4; k++) px[r][k] = cache[W::mul24(row[r][k], ntex) + W::mul24(cm[k] >> 8, rt.unit_y) + ty[r]];
+  }
+  // Inventory quad of a thread: its four finished texels are global loads -- issued before the per-frame tables are built
+  // (item_quad_issue), and placed when the frame goes out (item_quad_store).  Unconditional loads from clamped addresses
+  // (cell 0 when there is nothing to show), masked afterwards: a load under a lane predicate is waited for at the end of its
+  // predicated region, one load latency after the other.
+  // The inventory quads belong to the threads behind the first wave (which is busy with the cell table until the tables'
+  // barrier): quad q = tid - 64 + s * (threads - 64), KI of them per thread at most.
+  static constexpr int KI = 2;
+  static constexpr int kItemOwners = W::kThreads > 64 ? W::kThreads - 64 : W::kThreads;
+  static constexpr int kItemFirst = W::kThreads > 64 ? 64 : 0;
+  struct ItemQuad {
+    uint32_t px[KI][4];
+    bool show[KI][4];
+  };
+  __device__ __forceinline__ void item_quad_issue(ItemQuad& iq, int tid, const SmallDiv<W>& by_gpr, int item_quads) const {
+    const Config& c = e.cfg;
+    const int lw = c.local_gw * rt.unit_x, lh = c.local_gh * rt.unit_y, ntex = rt.unit_x * rt.unit_y, gpr = by_gpr.d;
+    const uint32_t* item_cells = (const uint32_t*)(e.tb.render_static + render_static_bytes(c));
+    int t0 = tid - kItemFirst;
+    int y0 = by_gpr.div(t0), g = t0 - by_gpr.mul(y0);   // the column group is t0 % gpr for every quad of the thread
+#pragma unroll
+    for (int s_ = 0; s_ < KI; s_++) {
+      int iy = y0 + s_ * (kItemOwners / gpr);
+      bool mine = W::mul24(iy, gpr) + g < item_quads;
+      int rm = rowmap[lh + (mine ? iy : 0)];
+      int cy = rm & 0xFF, ty = rm >> 8;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        int x = 4 * g + k;
+        int cm = colmap[x < lw ? x : lw - 1];
+        int slot = W::mul24(cy, c.item_gw) + (cm & 0xFF);
+        bool has = mine && x < lw && slot < e.R.n_items;
+        int amount = e.rec->inv[has ? slot : 0];
+        iq.show[s_][k] = has && amount >= 1;
+        int d = amount <= 9 ? amount : 10;   // engine.py:245: 'unknown' beyond 9
+        int at = W::mul24(W::mul24(slot, kItemDigits) + d, ntex) + W::mul24(cm >> 8, rt.unit_y) + ty;
+        iq.px[s_][k] = item_cells[iq.show[s_][k] ? at : 0];
+      }
+    }
+  }
+  __device__ __forceinline__ void item_quad_store(const ItemQuad& iq, int tid, const SmallDiv<W>& by_gpr, int item_quads) const {
+    const int lh = e.cfg.local_gh * rt.unit_y, gpr = by_gpr.d;
+    int t0 = tid - kItemFirst;
+    int iy0 = by_gpr.div(t0), g = t0 - by_gpr.mul(iy0);
+#pragma unroll
+    for (int s_ = 0; s_ < KI; s_++) {
+      int iy = iy0 + s_ * (kItemOwners / gpr);
+      if (W::mul24(iy, gpr) + g >= item_quads) continue;
+      uint32_t ipx[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) ipx[k] = iq.show[s_][k] ? iq.px[s_][k] : 0u;
+      store_quad(lh + iy, g, ipx);
+    }
   }
 
   // ---- Early frame (round 6): the part of a day frame that does not depend on the objects, drawn WHILE the object loop runs.
@@ -532,9 +653,7 @@ struct Renderer {
     constexpr int NP = NT > 64 ? NT - 64 : NT;
     constexpr int T0 = NT > 64 ? 64 : 0;
     const int ncell = c.local_gw * c.local_gh;
-    const int ntex = rt.unit_x * rt.unit_y;
-    const int lw = c.local_gw * rt.unit_x, lh = c.local_gh * rt.unit_y;
-    const int sw = rt.size_w, gpr = sw >> 2;
+    const int gpr = rt.size_w >> 2;
     if (w.wave_is(NT > 64 ? 1 : 0)) {   // the material half of the cell table, one lane per cell
       Obj p = e.obj_rd_lane(1);
       int offx = c.local_gw / 2, offy = c.local_gh / 2;
@@ -555,47 +674,10 @@ struct Renderer {
       if (w.lane() == 0) w.lds_inc(&hdr[2]);
     }
     w.spin_until(&hdr[2], (uint32_t)(W::kDrawingWaves + 1));     // every drawing wave's rows + the cell table
-    const int row_bytes = 3 * sw;
-    const int rows_per = NP / gpr;
     SmallDiv<W> by_gpr(gpr, NT);
-    struct Px4 { uint32_t a, b, c; };
     w.each_thread([&](int tid) {
       if (tid < T0) return;
-      int t = tid - T0;
-      int y0 = by_gpr.div(t), g = t - by_gpr.mul(y0);
-      int cm[4];
-      bool in[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        int x = 4 * g + k;
-        in[k] = x < lw;
-        cm[k] = colmap[in[k] ? x : lw - 1];
-      }
-      constexpr int KR = 5;
-      int yy[KR], rbase[KR], ty[KR], row[KR][4];
-      uint32_t px[KR][4];
-#pragma unroll
-      for (int r = 0; r < KR; r++) {
-        yy[r] = y0 + r * rows_per;
-        int rm = rowmap[yy[r] < lh ? yy[r] : lh - 1];
-        rbase[r] = rm & 0xFF;
-        ty[r] = rm >> 8;
-      }
-#pragma unroll
-      for (int r = 0; r < KR; r++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) row[r][k] = cell_row[W::mul24(cm[k] & 0xFF, c.local_gh) + rbase[r]];
-#pragma unroll
-      for (int r = 0; r < KR; r++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) px[r][k] = cache[W::mul24(row[r][k], ntex) + W::mul24(cm[k] >> 8, rt.unit_y) + ty[r]];
-#pragma unroll
-      for (int r = 0; r < KR; r++) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) px[r][k] = in[k] ? (px[r][k] & 0xFFFFFFu) : 0u;
-        Px4 v = {px[r][0] | (px[r][1] << 24), (px[r][1] >> 8) | (px[r][2] << 16), (px[r][2] >> 16) | (px[r][3] << 8)};
-        if (yy[r] < lh) *(Px4*)(rt.out + W::mul24(yy[r], row_bytes) + 12 * g) = v;
-      }
+      local_quads<5>(tid - T0, NP / gpr, by_gpr, [&](int, auto&, auto& cm, auto& yy, auto& px) { day_rows<5>(cm, yy, px); });
     });
     if (w.lane() == 0) w.lds_inc(&hdr[3]);
   }
@@ -615,45 +697,14 @@ struct Renderer {
     const int lw = c.local_gw * rt.unit_x, lh = c.local_gh * rt.unit_y, ih = c.item_gh * rt.unit_y;
     const int sw = rt.size_w, sh = rt.size_h, gpr = sw >> 2;
     const int item_quads = gpr * ih, tail_quads = gpr * (sh - lh - ih);
-    const int row_bytes = 3 * sw;
     SmallDiv<W> by_gpr(gpr, NT);
-    struct Px4 { uint32_t a, b, c; };
     // the inventory quads' texels: loads issued now, by the waves behind the first one (as in render)
-    constexpr int KI = 2;
-    constexpr int kItemOwners = NT > 64 ? NT - 64 : NT;
-    constexpr int kItemFirst = NT > 64 ? 64 : 0;
-    struct ItemQuad {
-      uint32_t px[KI][4];
-      bool show[KI][4];
-    };
     ItemQuad item_quad[W::kThreadSlots];
     const bool items_ok = item_quads <= KI * kItemOwners && kItemOwners % gpr == 0;
     if (items_ok) {
-      const uint32_t* item_cells = (const uint32_t*)(e.tb.render_static + render_static_bytes(c));
       w.each_thread([&](int tid) {
         if (!W::uni((int)(tid >= kItemFirst))) return;
-        ItemQuad& iq = item_quad[W::thread_slot(tid)];
-        int t0 = tid - kItemFirst;
-        int y0 = by_gpr.div(t0), g = t0 - by_gpr.mul(y0);
-#pragma unroll
-        for (int s_ = 0; s_ < KI; s_++) {
-          int iy = y0 + s_ * (kItemOwners / gpr);
-          bool mine = W::mul24(iy, gpr) + g < item_quads;
-          int rm = rowmap[lh + (mine ? iy : 0)];
-          int cy = rm & 0xFF, ty = rm >> 8;
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            int x = 4 * g + k;
-            int cm = colmap[x < lw ? x : lw - 1];
-            int slot = W::mul24(cy, c.item_gw) + (cm & 0xFF);
-            bool has = mine && x < lw && slot < e.R.n_items;
-            int amount = e.rec->inv[has ? slot : 0];
-            iq.show[s_][k] = has && amount >= 1;
-            int d = amount <= 9 ? amount : 10;
-            int at = W::mul24(W::mul24(slot, kItemDigits) + d, ntex) + W::mul24(cm >> 8, rt.unit_y) + ty;
-            iq.px[s_][k] = item_cells[iq.show[s_][k] ? at : 0];
-          }
-        }
+        item_quad_issue(item_quad[W::thread_slot(tid)], tid, by_gpr, item_quads);
       });
     }
     if (w.wave_is(0)) {
@@ -744,43 +795,20 @@ struct Renderer {
             int cmk = colmap[inside ? x : lw - 1];
             int row = cell_row[W::mul24(cmk & 0xFF, c.local_gh) + (rm & 0xFF)];
             uint32_t v = cache[W::mul24(row, ntex) + W::mul24(cmk >> 8, rt.unit_y) + (rm >> 8)];
-            q[kk] = inside ? (v & 0xFFFFFFu) : 0u;
+            q[kk] = inside ? v : 0u;
           }
-          Px4 v = {q[0] | (q[1] << 24), (q[1] >> 8) | (q[2] << 16), (q[2] >> 16) | (q[3] << 8)};
-          *(Px4*)(rt.out + W::mul24(y, row_bytes) + 12 * g) = v;
+          store_quad(y, g, q);
         }
       }
-      if (items_ok && W::uni((int)(tid >= kItemFirst))) {
-        const ItemQuad& iq = item_quad[W::thread_slot(tid)];
-        int t0 = tid - kItemFirst;
-        int iy0 = by_gpr.div(t0), g = t0 - by_gpr.mul(iy0);
-#pragma unroll
-        for (int si = 0; si < KI; si++) {
-          int iy = iy0 + si * (kItemOwners / gpr);
-          if (W::mul24(iy, gpr) + g >= item_quads) continue;
-          uint32_t ipx[4];
-#pragma unroll
-          for (int kk = 0; kk < 4; kk++) ipx[kk] = iq.show[si][kk] ? (iq.px[si][kk] & 0xFFFFFFu) : 0u;
-          Px4 v = {ipx[0] | (ipx[1] << 24), (ipx[1] >> 8) | (ipx[2] << 16), (ipx[2] >> 16) | (ipx[3] << 8)};
-          *(Px4*)(rt.out + W::mul24(lh + iy, row_bytes) + 12 * g) = v;
-        }
-      }
-      for (int gi = tid; gi < tail_quads; gi += NT) {
-        Px4 v = {0u, 0u, 0u};
-        *(Px4*)(rt.out + W::mul24(lh + ih, row_bytes) + 12 * gi) = v;
-      }
+      if (items_ok && W::uni((int)(tid >= kItemFirst))) item_quad_store(item_quad[W::thread_slot(tid)], tid, by_gpr, item_quads);
+      zero_tail(tid, lh + ih, tail_quads);
     });
     if (prof && w.leader()) prof[8] = w.clock();
     return true;
   }
   __device__ __forceinline__ bool finish_day_frame(double daylight) {
-    Lit L;
-    L.D = daylight;
-    L.iD = 1 - L.D;
-    L.hD = L.iD * 0.5;
-    L.night = false;
-    L.sleeping = e.rec->sleeping != 0;
-    L.amount = 2 * (0.5 - L.D);
+    Lit L(daylight, e.rec->sleeping != 0);
+    L.night = false;   // (an early frame is a day frame: said to the compiler)
     return finish_frame(L);
   }
 
@@ -823,11 +851,7 @@ struct Renderer {
     // the raw rows come back first.
     const bool rows_lit = cache && !L.night && rows_step == e.rec->step && rows_sleeping == L.sleeping;
     if (cache && !rows_lit && rows_step >= 0) {
-      const vec16* src = (const vec16*)(e.tb.render_static + render_static_bytes(c) - texel_cache_bytes(c));
-      vec16* dst = (vec16*)cache;
-      const int words = kSpriteRow0 * ntex;   // (not a byte beyond the material rows: the first wave is about to write the sprite rows behind them)
-      w.block_for(words / 4, [&](int i) { dst[i] = src[i]; });   // (read behind the tables' barrier below)
-      w.block_for(words & 3, [&](int i) { cache[(words & ~3) + i] = ((const uint32_t*)src)[(words & ~3) + i]; });
+      copy_material_rows(raw_rows(), [&](int n, auto f) { w.block_for(n, f); });   // (read behind the tables' barrier below)
       rows_step = -1;
     }
     if (w.wave_is(0)) {
@@ -1069,7 +1093,6 @@ struct Renderer {
   // next epoch's pixels in flight (the only global loads of the pass).
   __device__ __forceinline__ void noise_pass(const Lit& L, int mode, int lw, int lh) {
     W& w = e.w;
-    const Config& c = e.cfg;
     int sw = rt.size_w;
     int total = lw * lh;
     int words = 2 * total;
@@ -1088,8 +1111,7 @@ struct Renderer {
     bool shader = w.consumer_slot(overlap, q0, qs);
     constexpr int K = W::kEpochSlots;
     bool tabled = mode == 1 && cache != nullptr && (int)hdr[1] <= kSpriteRows;   // row table + pixel records
-    const NightPx* npx = (const NightPx*)(e.tb.render_static + render_static_bytes(c) + render_item_cells_bytes(c) +
-                                          render_lit_bytes(c));
+    const NightPx* npx = night_px();
     double vcur[K], vnext[K];
     uint32_t dcur[K], dnext[K];
     auto epoch_first = [&](int s_lo_) { return s_lo_ >> 1; };                       // odd s_lo: first word is the carry
@@ -1211,10 +1233,9 @@ struct Renderer {
   // leaves them in `pix` in stream order, where the quads pick them up exactly as after noise_pass.
   __device__ __forceinline__ void noise_pass_ahead(const Lit& L, int lw, int lh) {
     W& w = e.w;
-    const Config& c = e.cfg;
     constexpr int NT = W::kThreads;
     const int total = lw * lh, ntex = rt.unit_x * rt.unit_y;
-    const NightPx* npx = (const NightPx*)(e.tb.render_static + render_static_bytes(c) + render_item_cells_bytes(c) + render_lit_bytes(c));
+    const NightPx* npx = night_px();
     const uint32_t* words = noise_raw + noise_base;
     w.each_thread([&](int tid) {
       constexpr int D = 2;   // pixels whose loads are in flight ahead of the one being lit
@@ -1267,13 +1288,7 @@ struct Renderer {
     W& w = e.w;
     int lw = c.local_gw * rt.unit_x, lh = c.local_gh * rt.unit_y;
     int ih = c.item_gh * rt.unit_y;
-    Lit L;
-    L.D = (e.rec->step == hint_step) ? hint_D : e.tb.daylight[e.rec->step];
-    L.iD = 1 - L.D;
-    L.hD = L.iD * 0.5;
-    L.night = L.D < 0.5;
-    L.sleeping = e.rec->sleeping != 0;
-    L.amount = 2 * (0.5 - L.D);
+    Lit L((e.rec->step == hint_step) ? hint_D : e.tb.daylight[e.rec->step], e.rec->sleeping != 0);
     int sw = rt.size_w, sh = rt.size_h;
     if (L.night) e.mark_mt_rewritten();   // a night frame's noise regenerates the stream's state ten times over, drawn or not
     if (!pixels) {
@@ -1284,51 +1299,16 @@ struct Renderer {
     constexpr int KR = NT == 512 ? 2 : NT >= 256 ? 4 : NT >= 192 ? 5 : 13;   // LocalView rows of a thread whose look-up chains run side by side (16 quads per row: 49 rows <= KR * NT / 16)
     int gpr = sw >> 2;
     int item_quads = gpr * ih, tail_quads = gpr * (sh - lh - ih);
-    int ntex = rt.unit_x * rt.unit_y;
     bool quads = cache != nullptr && pix != nullptr && rt.border_x == 0 && rt.border_y == 0 && (sw & 3) == 0 && lw <= sw &&
                  NT % gpr == 0 && lh <= KR * (NT / gpr) && tail_quads >= 0 && c.item_gw == c.local_gw;
     SmallDiv<W> by_gpr(gpr, NT);
-    // Inventory quad of the thread (quad mode): its four finished texels are global loads -- issued now, before the
-    // per-frame tables are built, and placed when the frame goes out.  Unconditional loads from clamped addresses (cell 0
-    // when there is nothing to show), masked afterwards: a load under a lane predicate is waited for at the end of its
-    // predicated region, one load latency after the other.
-    // The inventory quads belong to the threads behind the first wave (which is busy with the cell table until the
-    // tables' barrier): quad q = tid - 64 + s * (threads - 64), KI of them per thread at most.
-    constexpr int KI = 2;
-    constexpr int kItemOwners = NT > 64 ? NT - 64 : NT;
-    constexpr int kItemFirst = NT > 64 ? 64 : 0;
-    struct ItemQuad {
-      uint32_t px[KI][4];
-      bool show[KI][4];
-    };
+    // the inventory quads' texels (quad mode): loads issued now, before the per-frame tables are built
     ItemQuad item_quad[W::kThreadSlots];
     quads = quads && item_quads <= KI * kItemOwners && kItemOwners % gpr == 0 && kItemFirst % gpr == 0;
     if (quads) {
-      const uint32_t* item_cells = (const uint32_t*)(e.tb.render_static + render_static_bytes(c));
       w.each_thread([&](int tid) {
         if (!W::uni((int)(tid >= kItemFirst))) return;   // a whole-wave (scalar) branch: the first wave skips the code, not just its lanes
-        ItemQuad& iq = item_quad[W::thread_slot(tid)];
-        int t0 = tid - kItemFirst;
-        int y0 = by_gpr.div(t0), g = t0 - by_gpr.mul(y0);   // the column group is tid % gpr for every quad of the thread
-#pragma unroll
-        for (int s_ = 0; s_ < KI; s_++) {
-          int iy = y0 + s_ * (kItemOwners / gpr);
-          bool mine = W::mul24(iy, gpr) + g < item_quads;
-          int rm = rowmap[lh + (mine ? iy : 0)];
-          int cy = rm & 0xFF, ty = rm >> 8;
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            int x = 4 * g + k;
-            int cm = colmap[x < lw ? x : lw - 1];
-            int slot = W::mul24(cy, c.item_gw) + (cm & 0xFF);
-            bool has = mine && x < lw && slot < e.R.n_items;
-            int amount = e.rec->inv[has ? slot : 0];
-            iq.show[s_][k] = has && amount >= 1;
-            int d = amount <= 9 ? amount : 10;   // engine.py:245: 'unknown' beyond 9
-            int at = W::mul24(W::mul24(slot, kItemDigits) + d, ntex) + W::mul24(cm >> 8, rt.unit_y) + ty;
-            iq.px[s_][k] = item_cells[iq.show[s_][k] ? at : 0];
-          }
-        }
+        item_quad_issue(item_quad[W::thread_slot(tid)], tid, by_gpr, item_quads);
       });
     }
     build_tables(L, !quads);
@@ -1340,27 +1320,13 @@ struct Renderer {
       const bool ahead = L.night && noise_raw != nullptr && (int)hdr[1] <= kSpriteRows && noise_base + 2 * lw * lh <= kAheadWords;
       if (ahead) noise_pass_ahead(L, lw, lh);             // ends on a barrier
       else if (L.night) noise_pass(L, 1, lw, lh);         // ends on a barrier
-      int row_bytes = 3 * sw;
-      int rows_per = NT / gpr;
-      struct Px4 { uint32_t a, b, c; };
+      const int rows_per = NT / gpr;
       w.each_thread([&](int tid) {
         // the thread's quads all sit in column group g = tid % gpr, in rows tid / gpr + n * (threads / gpr)
-        int y0 = by_gpr.div(tid), g = tid - by_gpr.mul(y0);
-        int cm[4];
-        bool in[4];
+        local_quads<KR>(tid, rows_per, by_gpr, [&](int g, auto& in, auto& cm, auto& yy, auto& px) {
+          if (!L.night) return day_rows<KR>(cm, yy, px);
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-          int x = 4 * g + k;
-          in[k] = x < lw;   // beyond the view: untouched canvas
-          cm[k] = colmap[in[k] ? x : lw - 1];
-        }
-        int yy[KR];
-        uint32_t px[KR][4];
-#pragma unroll
-        for (int r = 0; r < KR; r++) yy[r] = y0 + r * rows_per;
-        if (L.night) {
-#pragma unroll
-          for (int r = 0; r < KR; r++) {
+          for (int r = 0; r < KR; r++) {   // the pixels the noise pass left in `pix`, transposed
             int y = yy[r] < lh ? yy[r] : lh - 1;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -1368,51 +1334,9 @@ struct Renderer {
               px[r][k] = pix_global ? W::load_fresh(at) : *at;
             }
           }
-        } else {
-          // stage by stage over the thread's rows (clamped instead of predicated, only the store is guarded): row map,
-          // cell rows, texels -- up to 16 independent chains in flight
-          int rbase[KR], ty[KR], row[KR][4];
-#pragma unroll
-          for (int r = 0; r < KR; r++) {
-            int rm = rowmap[yy[r] < lh ? yy[r] : lh - 1];
-            rbase[r] = rm & 0xFF;
-            ty[r] = rm >> 8;
-          }
-#pragma unroll
-          for (int r = 0; r < KR; r++)
-#pragma unroll
-            for (int k = 0; k < 4; k++) row[r][k] = cell_row[W::mul24(cm[k] & 0xFF, c.local_gh) + rbase[r]];
-#pragma unroll
-          for (int r = 0; r < KR; r++)
-#pragma unroll
-            for (int k = 0; k < 4; k++) px[r][k] = cache[W::mul24(row[r][k], ntex) + W::mul24(cm[k] >> 8, rt.unit_y) + ty[r]];
-        }
-#pragma unroll
-        for (int r = 0; r < KR; r++) {
-#pragma unroll
-          for (int k = 0; k < 4; k++) px[r][k] = in[k] ? (px[r][k] & 0xFFFFFFu) : 0u;
-          Px4 v = {px[r][0] | (px[r][1] << 24), (px[r][1] >> 8) | (px[r][2] << 16), (px[r][2] >> 16) | (px[r][3] << 8)};
-          if (yy[r] < lh) *(Px4*)(rt.out + W::mul24(yy[r], row_bytes) + 12 * g) = v;
-        }
-        if (W::uni((int)(tid >= kItemFirst))) {
-          const ItemQuad& iq = item_quad[W::thread_slot(tid)];
-          int t0 = tid - kItemFirst;
-          int iy0 = by_gpr.div(t0);
-#pragma unroll
-          for (int s_ = 0; s_ < KI; s_++) {
-            int iy = iy0 + s_ * (kItemOwners / gpr);
-            if (W::mul24(iy, gpr) + g >= item_quads) continue;
-            uint32_t ipx[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) ipx[k] = iq.show[s_][k] ? (iq.px[s_][k] & 0xFFFFFFu) : 0u;
-            Px4 v = {ipx[0] | (ipx[1] << 24), (ipx[1] >> 8) | (ipx[2] << 16), (ipx[2] >> 16) | (ipx[3] << 8)};
-            *(Px4*)(rt.out + W::mul24(lh + iy, row_bytes) + 12 * g) = v;
-          }
-        }
-        for (int gi = tid; gi < tail_quads; gi += NT) {
-          Px4 v = {0u, 0u, 0u};
-          *(Px4*)(rt.out + W::mul24(lh + ih, row_bytes) + 12 * gi) = v;
-        }
+        });
+        if (W::uni((int)(tid >= kItemFirst))) item_quad_store(item_quad[W::thread_slot(tid)], tid, by_gpr, item_quads);
+        zero_tail(tid, lh + ih, tail_quads);
       });
       if (ahead) {   // the stream moved on by the frame's 2 * lw * lh words: the state it stopped in comes back from the scratch
         int end = noise_base + 2 * lw * lh;              // words consumed since the staged state's first one
