@@ -216,18 +216,29 @@ crafter_reset_worlds_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_
 
 // World pool generation (side streams): three kernels per batch, each walking the batch's segment of the request queue
 // (gen_bodies.hpp gen_seed_body / gen_classify_body / gen_resolve_body).  GEO as for the step kernel.
+// The queue head they open with: the segment of `parity` (pool_entry.hpp: count, 3 pad, (env, episode) pairs), its count clamped
+// to the segment's capacity.
+struct GenQueue {
+  const int32_t* q;
+  int count;
+  __device__ __forceinline__ int env(int k) const { return q[4 + 2 * k]; }
+  __device__ __forceinline__ int episode(int k) const { return q[4 + 2 * k + 1]; }
+};
+__device__ __forceinline__ GenQueue gen_queue(const Config& cfg, const StatePtrs& st, int parity) {
+  const int32_t* q = st.gen_q + (size_t)parity * gen_q_stride(cfg);
+  return {q, q[0] > gen_q_capacity(cfg) ? gen_q_capacity(cfg) : q[0]};
+}
+
 template <int GEO>
 __global__ void __launch_bounds__(kGenSeedThreads)
 crafter_gen_seed_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parity, int prio, const LevelTable* __restrict__ levels) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   WaveGfx950<kGenSeedThreads>::set_priority(prio);   // (pool_schedule: one wave per world, a chain -- see there)
   const Config cfg = GEO ? with_default_geometry(cfg_in) : cfg_in;
-  const int32_t* q = st.gen_q + (size_t)parity * gen_q_stride(cfg);
-  int count = q[0];
-  if (count > gen_q_capacity(cfg)) count = gen_q_capacity(cfg);
+  const GenQueue gq = gen_queue(cfg, st, parity);
   WaveGfx950<kGenSeedThreads> w;
-  for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
-    gen_seed_body(w, smem, q[4 + 2 * k], q[4 + 2 * k + 1], cfg, tb, st, levels);
+  for (int k = (int)blockIdx.x; k < gq.count; k += (int)gridDim.x) {
+    gen_seed_body(w, smem, gq.env(k), gq.episode(k), cfg, tb, st, levels);
     __syncthreads();
   }
 }
@@ -241,14 +252,12 @@ crafter_gen_classify_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parit
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   WaveGfx950<kGenClassifyThreads>::set_priority(prio);
   const Config cfg = GEO ? with_default_geometry(cfg_in) : cfg_in;
-  const int32_t* q = st.gen_q + (size_t)parity * gen_q_stride(cfg);
-  int count = q[0];
-  if (count > gen_q_capacity(cfg)) count = gen_q_capacity(cfg);
+  const GenQueue gq = gen_queue(cfg, st, parity);
   WaveGfx950<kGenClassifyThreads> w;
   const int parts = gen_classify_parts(cfg);
-  for (int item = (int)blockIdx.x; item < count * parts; item += (int)gridDim.x) {
+  for (int item = (int)blockIdx.x; item < gq.count * parts; item += (int)gridDim.x) {
     int k = item / parts;
-    gen_classify_body(w, smem, q[4 + 2 * k], q[4 + 2 * k + 1], item - k * parts, parts, cfg, tb, st);
+    gen_classify_body(w, smem, gq.env(k), gq.episode(k), item - k * parts, parts, cfg, tb, st);
     __syncthreads();
   }
 }
@@ -259,12 +268,10 @@ crafter_gen_resolve_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parity
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   WaveGfx950<kGenResolveThreads>::set_priority(prio);
   const Config cfg = GEO ? with_default_geometry(cfg_in) : cfg_in;
-  const int32_t* q = st.gen_q + (size_t)parity * gen_q_stride(cfg);
-  int count = q[0];
-  if (count > gen_q_capacity(cfg)) count = gen_q_capacity(cfg);
+  const GenQueue gq = gen_queue(cfg, st, parity);
   WaveGfx950<kGenResolveThreads> w;
-  for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
-    gen_resolve_body(w, smem, q[4 + 2 * k], q[4 + 2 * k + 1], seq, cfg, tb, st);
+  for (int k = (int)blockIdx.x; k < gq.count; k += (int)gridDim.x) {
+    gen_resolve_body(w, smem, gq.env(k), gq.episode(k), seq, cfg, tb, st);
     __syncthreads();
   }
 }
@@ -295,12 +302,10 @@ __global__ void __launch_bounds__(kStepThreads)
 crafter_gen_stamp_kernel(Config cfg_in, TablePtrs tb, StatePtrs st, int parity, uint32_t seq) {
   typedef WaveGfx950<kStepThreads> WS;
   const Config cfg = GEO ? with_default_geometry(cfg_in) : cfg_in;
-  const int32_t* q = st.gen_q + (size_t)parity * gen_q_stride(cfg);
-  int count = q[0];
-  if (count > gen_q_capacity(cfg)) count = gen_q_capacity(cfg);
+  const GenQueue gq = gen_queue(cfg, st, parity);
   const int cells = cfg.W * cfg.H, nch = cfg.nchunk_x * cfg.nchunk_y;
-  for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
-    int env = q[4 + 2 * k], episode = q[4 + 2 * k + 1];
+  for (int k = (int)blockIdx.x; k < gq.count; k += (int)gridDim.x) {
+    int env = gq.env(k), episode = gq.episode(k);
     size_t slot = pool_slot(cfg, env, episode), other = pool_slot(cfg, env, episode + 1);
     PoolHdr* h = st.pool_hdr + slot;
     bool skip = !gen_wanted<WS>(st, env, episode) || gen_done_already<WS>(cfg, st, env, episode);

@@ -1,6 +1,6 @@
 // Level sets (crafter_set_levels) supersede what DESIGN.md 9.0 assumed about a device-side level sampler inside the auto-reset:
-// it needs NO pool keyed by (lane, episode).  A world is seeded at three sites only -- WorldGen::reset_env, gen_body,
-// gen_seed_body -- and all three call level_seed(table, lane, k) below: with a table the level of the env's k-th reset is a pure
+// it needs NO pool keyed by (lane, episode).  A generated world is seeded by WorldGen::seed_world alone (worldgen.hpp), which
+// both forms of the generator hand level_seed(table, lane, k) below: with a table the level of the env's k-th reset is a pure
 // function of (the env's own seed lane, k, the table), so the pool keeps keying its entries by k, the inline and the pooled path
 // agree by construction, and entries only have to be emptied when the table itself is replaced (set_levels_body).
 //

@@ -5,8 +5,9 @@
 // particular order.  So the caller's records are not copied into the row: they are REPLAYED through Env::obj_add / obj_move
 // (env_core.hpp), the same calls worldgen makes, in record order, and everything derived comes out as the reference's.
 //
-//   author_world   : World.reset + RandomState(world seed) + the player at the centre (exactly what WorldGen::reset_env does
-//                    in front of generate_world), then the authored function -- the map, the records, the inventory
+//   author_world   : World.reset and RandomState(world seed) -- the generator's own stages, WorldGen::world_reset and
+//                    seed_stream (worldgen.hpp) -- the player at the centre, then the authored function: the map, the
+//                    records, the inventory
 //   reset_world_body : reset_body (reset_bodies.hpp: the same reset_skeleton) with author_world where reset_env stands
 //
 // The bank comes from a caller and is never trusted: a value that would index outside a table is repaired or its record is
@@ -48,7 +49,6 @@ __device__ __forceinline__ void author_world(WorldGen<W, S>& wg, const LevelTabl
   const Rules& R = e.R;
   EnvRec* rec = e.rec;
   const int cells = c.W * c.H;
-  const int nch = c.nchunk_x * c.nchunk_y;
   const int episode = rec->episode + 1;
   const uint32_t wseed = level_seed(levels, rec->seed_lane, episode);   // env.py:74, as reset_env seeds it
   w.sync();
@@ -61,13 +61,7 @@ __device__ __forceinline__ void author_world(WorldGen<W, S>& wg, const LevelTabl
       rec->inv[i] = v < 0 ? 0 : v > R.item_max[i] ? R.item_max[i] : v;
     });
   }
-  // World.reset engine.py:33-39 (reset_env's own prologue, which stays as it is: that function goes on into the generator)
-  w.block_for(cells, [&](int i) {
-    if (e.objmap) e.objmap[i] = 0;
-    if (e.g_objmap && (const void*)e.g_objmap != (const void*)e.objmap) e.g_objmap[i] = 0;
-  });
-  w.block_for(nch, [&](int i) { e.chunk_seen[i] = 0; e.chunk_order[i] = 0; });
-  e.clear_creature_counts();
+  wg.world_reset();
   // the material map: bank -> registers -> the LDS copy and the env's map in global memory, 16 bytes per load where both
   // rows are aligned, byte by byte for what is left.  A byte that names no material becomes grass on the way.
   {
@@ -99,16 +93,7 @@ __device__ __forceinline__ void author_world(WorldGen<W, S>& wg, const LevelTabl
     });
     if (bad) w.lds_or(&rec->status, ST_BAD_WORLD);
   }
-  if (w.wave0()) {
-    wg.init_mt(wseed);
-    e.st(&rec->nchunks_seen, 0);
-    Obj z;
-    z.type = T_NONE; z.health = 0; z.fx = 0; z.fy = 0; z.x = 0; z.y = 0; z.aux = 0; z.pad = 0;
-    e.st(e.objs, z);
-  }
-  e.mt_pos = MT_N;
-  e.nobj = 1;
-  e.dirty_slots = 0;
+  wg.seed_stream(wseed);
   w.sync();
   if (w.wave0()) {
     const int px = c.W / 2, py = c.H / 2;

@@ -79,8 +79,10 @@ __device__ __forceinline__ void gen_body(W& w, uint8_t* smem, int env, int episo
 }
 
 // ---------------------------------------------------------------------------------------------
-// World-pool generation as a pipeline of three kernels (same arithmetic as gen_body, which stays as the fused form
-// crafter_reset_kernel appends).  Generating a world is 5 % seeding (serial: init_genrand, the OpenSimplex
+// World-pool generation as a pipeline of three kernels: the stages of WorldGen (worldgen.hpp "the generator's stages") that
+// reset_env -- and with it gen_body, the fused form crafter_reset_kernel appends -- runs back to back, here with the pool entry
+// in between: seed_world | classify_head / classify_lookup / classify_advance | world_reset, draw_world, strip_flags.
+// Generating a world is 5 % seeding (serial: init_genrand, the OpenSimplex
 // shuffle), 50 % terrain noise (parallel over cells, 128 VGPRs of f64) and 45 % ordered uniform() draws (serial, one
 // wave).  In one 1024-thread workgroup the serial half holds a whole CU's registers while 15 waves sleep at a barrier;
 // split by kind of parallelism, every piece is sized for what it does and fits NEXT TO the step kernel's workgroups:
@@ -116,17 +118,7 @@ __device__ __forceinline__ void gen_seed_body(W& w, uint8_t* smem, int env, int 
   WorldGen<W> wg(e, smem + align16(4 * MT_N));
   uint32_t wseed = level_seed(levels, st.rec[env].seed_lane, episode);   // env.py:74
   GEN_T0
-  if (w.wave0()) wg.init_mt(wseed);
-  e.mt_pos = MT_N;
-  e.rng_invalidate();
-  w.sync();
-  GEN_STAMP(0);
-  uint32_t sseed = 0;
-  if (w.wave0()) sseed = e.randint(2147483647u);   // worldgen.py:11
-  sseed = w.bcast_from_wave0(sseed);
-  GEN_STAMP(1);
-  wg.seed_simplex((int64_t)sseed);
-  GEN_STAMP(2);
+  wg.seed_world(wseed, false, [&](int k) { GEN_STAMP(k); });   // slots 0 .. 2; the tables are gen_classify_body's to fill: this LDS ends in front of them
   GEN_COUNT(7);
   e.mt_pos = (int)w.bcast_from_wave0((uint32_t)e.mt_pos);   // wave 0's stream position -> every wave (single-wave workgroups: a no-op)
   size_t slot = pool_slot(cfg, env, episode);
@@ -235,40 +227,16 @@ __device__ __forceinline__ void gen_resolve_body(W& w, uint8_t* smem, int env, i
   if (e.mat != e.g_mat) copy_map_in(e);
   const uint32_t* gmt = st.pool_mt + slot * MT_N;
   w.block_for(MT_N, [&](int i) { e.mt[i] = gmt[i]; });
-  w.block_for(nch, [&](int i) { e.chunk_seen[i] = 0; e.chunk_order[i] = 0; });
-  e.clear_creature_counts();
-  if (w.leader()) {
-    e.rec->status = 0;
-    e.rec->nchunks_seen = 0;
-    Obj z;
-    z.type = T_NONE; z.health = 0; z.fx = 0; z.fy = 0; z.x = 0; z.y = 0; z.aux = 0; z.pad = 0;
-    e.objs[0] = z;
-  }
-  e.mt_pos = st.pool_hdr[slot].mt_pos;
-  e.nobj = 1;
-  e.dirty_slots = 0;
+  WorldGen<W> wg(e, smem + G.wg);
+  wg.world_reset();
+  e.st(&e.rec->status, 0);
+  e.mt_pos = st.pool_hdr[slot].mt_pos;   // the stream as gen_seed_body left it: one draw in
   e.rng_invalidate();
   w.sync();
-  WorldGen<W> wg(e, smem + G.wg);
-  int px = cfg.W / 2, py = cfg.H / 2;
   GEN_STAMP(16);
-  if (w.wave0()) {
-    e.obj_add(T_PLAYER, px, py, 0, 0, 1, 0);   // facing (0, 1) objects.py:72; slot 1
-    wg.window_open();
-    GEN_STAMP(17);
-    wg.resolve_materials(cells);
-    GEN_STAMP(18);
-    wg.place_creatures(cells, px, py);
-    GEN_STAMP(19);
-  }
-  w.sync();
+  wg.draw_world(cells, [&](int k) { GEN_STAMP(17 + k); });   // slots 17 .. 19
   share_registers(e);
-  w.block_for(cells, [&](int i) {   // strip the generation flags
-    uint8_t m = (uint8_t)(e.mat[i] & WG_MAT_MASK);
-    e.mat[i] = m;
-    e.g_mat[i] = m;
-  });
-  w.sync();
+  wg.strip_flags(cells);
   GEN_STAMP(20);
   e.recount_space();   // the world's grass / path counts per chunk travel with it (adopt_world copies them)
   GEN_STAMP(21);

@@ -8,7 +8,8 @@ namespace crafter {
 // every env is generated ahead of time by gen_body on a side stream and adopted by the step kernel
 // the moment the env finishes; Env.reset's worldgen then never sits on the step's critical path.
 // Whether an env adopts a pooled world or falls back to reset_body is unobservable: both run the
-// same generator on the same (seed, episode).
+// same stages of the one generator (worldgen.hpp "the generator's stages") on the same (seed, episode);
+// tests/test_generator_forms_host.py and tests/test_gpu_generator_forms.py compare their worlds field by field.
 
 // The pool runs TWO worlds ahead of every env (its two entries, by episode parity): when the env enters episode k it
 // asks for every world up to k + 2 that has not been asked for yet -- in steady state exactly one, world k + 2, which is

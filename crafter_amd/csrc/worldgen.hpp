@@ -100,6 +100,13 @@ __device__ __attribute__((noinline)) static double exp_cr(double x) {
   return __builtin_fabs(x) <= 0x1p-52 ? tiny : out;
 }
 
+// the record of slot 0, which names no object (World.reset: engine.py:33-39)
+__device__ __forceinline__ Obj zero_obj() {
+  Obj z;
+  z.type = T_NONE; z.health = 0; z.fx = 0; z.fy = 0; z.x = 0; z.y = 0; z.aux = 0; z.pad = 0;
+  return z;
+}
+
 template <class W, class S = uint16_t>   // S: the slot map's element type of the Env it generates into (env_core.hpp)
 struct WorldGen {
   Env<W, S>& e;
@@ -122,8 +129,9 @@ struct WorldGen {
 
   // OpenSimplex(seed) permutation (SURVEY App. B "Seeding"): the 256 LCG draws are independent
   // given the seed (jump-ahead per thread); only the shuffle itself is a serial chain, one LDS
-  // round trip per element.
-  __device__ __forceinline__ void seed_simplex(int64_t seed) {
+  // round trip per element.  tables: noise3's tables behind it too (not where only the permutation is wanted and the LDS ends
+  // in front of them: gen_seed_body).
+  __device__ __forceinline__ void seed_simplex(int64_t seed, bool tables) {
     e.w.block_for(256, [&](int i) { ridx[i] = (uint8_t)simplex_shuffle_index(seed, i); });
     e.w.sync();
     e.w.block_for(256, [&](int i) { source[i] = (uint8_t)i; });
@@ -151,7 +159,7 @@ struct WorldGen {
     }
     e.w.sync();
     e.w.block_for(256, [&](int i) { pg3[i] = (uint8_t)(perm[i] % 24); });   // Simplex::contrib
-    fill_gradients();
+    if (tables) fill_gradients();
     e.w.sync();
   }
 
@@ -187,7 +195,7 @@ struct WorldGen {
   //     1.9e-13, whatever flavour of exp: `start > 0.5` is false, water moves by 2 start <= 3.8e-13 and mountain by
   //     4 start + 0.3 x 2 start <= 8.8e-13 (+ a few ulps of re-rounding, 1e-16);
   //   * with start taken as 0 the two fields are therefore within 1e-12 of their true values, and every comparison against
-  //     them (water: 0.25, 0.3, 0.35; mountain: 0.15, 0.18, 0.3 -- classify / classify_head / resolve's flags) comes out the
+  //     them (water: 0.25, 0.3, 0.35; mountain: 0.15, 0.18, 0.3 -- all made in classify_head) comes out the
   //     same PROVIDED neither field lies within kGuard = 1e-11 of one of its thresholds: that is checked, per cell, and a
   //     cell that fails the check (about one in 10^10) is evaluated in full.
   // tests/test_worldgen_guard.py: 1,000+ worlds of 256x256 and 64x64 generated both ways by the same code (CRAFTER_WG_NO_SKIP),
@@ -220,35 +228,28 @@ struct WorldGen {
     mountain = m0 - (4 * start + 0.3 * water);
   }
 
-  // worldgen.py:21-61 up to (not including) the uniform() draws
-  __device__ __forceinline__ static uint8_t classify(const Simplex<W>& sx, const ClassIds& R, int x, int y, int px, int py) {
-    double fx = (double)x, fy = (double)y;
-    double start, water, mountain;
-    terrain_fields(sx, x, y, px, py, start, water, mountain);
-    if (start > 0.5) return (uint8_t)R.grass;
-    if (mountain > 0.15) {
-      if (S1(sx, fx, fy, 6, 7) > 0.15 && mountain > 0.3) return (uint8_t)R.path;          // cave
-      if (S1(sx, (double)(2 * x), fy / 5, 7, 3) > 0.4) return (uint8_t)(R.path | WG_TUNNEL);  // horizontal tunnel
-      if (S1(sx, fx / 5, (double)(2 * y), 7, 3) > 0.4) return (uint8_t)(R.path | WG_TUNNEL);  // vertical tunnel
-      int c1 = S1(sx, fx, fy, 1, 8) > 0;
-      int c2 = S1(sx, fx, fy, 2, 6) > 0.4;
-      int c3 = mountain > 0.18;
-      int c4 = mountain > 0.3 && S1(sx, fx, fy, 6, 5) > 0.35;
-      if (!(c1 | c2 | c3)) return (uint8_t)(c4 ? R.lava : R.stone);
-      return (uint8_t)(WG_PENDING | c1 | (c2 << 1) | (c3 << 2) | (c4 << 3));
-    }
-    if (0.25 < water && water <= 0.35 && S1(sx, fx, fy, 4, 9) > -0.2) return (uint8_t)R.sand;
-    if (0.3 < water) return (uint8_t)R.water;
-    if (S1(sx, fx, fy, 5, 7) > 0) return (uint8_t)(WG_PENDING | WG_TREE);
-    return (uint8_t)R.grass;
-  }
-
-  // ---- classification in compacted passes (the world pool's classification kernel) ---------------------------------
-  // classify() above evaluates its conditional noise look-ups under divergence: a wave runs every branch any of its
-  // lanes takes, ~10 noise3 per wave-cell for 6.3 needed per cell.  Here the five unconditional look-ups are evaluated
-  // for all cells first; what each cell still needs is a little state machine (next look-up + condition bits), and
-  // every round gathers the cells that need a look-up -- of whatever kind: they all run the same noise3 -- into a dense
-  // list, one lane per entry.  Same expressions, same comparisons, same results as classify().
+  // ---- the terrain decision tree, worldgen.py:21-61 up to (not including) the uniform() draws ----------------------------
+  // Stated once, as a little state machine per cell: classify_head evaluates the five unconditional look-ups (terrain_fields)
+  // and returns either the cell's final code or the first conditional look-up it needs; classify_lookup evaluates the look-up a
+  // state names -- they all run the same noise3, only (x, y, size, z) differ --; classify_advance applies its value and returns
+  // the next state, with the final code once that is NK_DONE.  The tree, with simplex(x, y, z, size) as worldgen.py:79 writes it:
+  //   start > 0.5                                                        grass (around the player)
+  //   mountain > 0.15:
+  //     NK_CAVES  simplex(x, y, 6, 7) > 0.15 and mountain > 0.3          path (cave)
+  //     NK_TUNH   simplex(2 x, y / 5, 7, 3) > 0.4                        path | WG_TUNNEL (horizontal tunnel)
+  //     NK_TUNV   simplex(x / 5, 2 y, 7, 3) > 0.4                        path | WG_TUNNEL (vertical tunnel)
+  //     NK_C1     c1 = simplex(x, y, 1, 8) > 0                           (coal's condition: one uniform() draw if set)
+  //     NK_C2     c2 = simplex(x, y, 2, 6) > 0.4                         (iron's; c3 = mountain > 0.18 is diamond's)
+  //     NK_C4     c4 = mountain > 0.3 and simplex(x, y, 6, 5) > 0.35     (lava's; looked up only if mountain > 0.3)
+  //               none of c1 c2 c3: lava if c4 else stone; otherwise WG_PENDING | c1 | c2 << 1 | c3 << 2 | c4 << 3
+  //   0.25 < water <= 0.35:
+  //     NK_SAND   simplex(x, y, 4, 9) > -0.2                             sand; else water if water > 0.3, else on to NK_TREE
+  //   water > 0.3                                                        water
+  //   otherwise:
+  //     NK_TREE   simplex(x, y, 5, 7) > 0                                WG_PENDING | WG_TREE (one draw), else grass
+  // Two schedules run it.  classify() below runs one cell to its end in one lane (the fused form, reset_env): a wave runs every
+  // state any of its lanes is in, ~10 noise3 per wave-cell for 6.3 needed per cell.  gen_classify_body (gen_bodies.hpp) evaluates
+  // classify_head for all its cells first; every round then gathers the cells that still need a look-up into a dense list.
   enum : int { NK_CAVES = 0, NK_TUNH, NK_TUNV, NK_C1, NK_C2, NK_C4, NK_SAND, NK_TREE, NK_DONE = 15 };
   enum : int { NF_M18 = 0x10, NF_M30 = 0x20, NF_A = 0x40, NF_B = 0x80 };   // mountain > 0.18, > 0.3; branch-specific: c1 / water > 0.3, c2
 
@@ -317,6 +318,14 @@ struct WorldGen {
         code = v > 0 ? (uint8_t)(WG_PENDING | WG_TREE) : R.grass;
         return NK_DONE;
     }
+  }
+
+  // one cell to its end, by one lane
+  __device__ __forceinline__ static uint8_t classify(const Simplex<W>& sx, const ClassIds& R, int x, int y, int px, int py) {
+    int st;
+    uint8_t code = classify_head(sx, R, x, y, px, py, st);
+    while ((st & 15) != NK_DONE) st = classify_advance(R, st, classify_lookup(sx, st, x, y), code);
+    return code;
   }
 
   // ---- random access into the env's MT19937 stream -------------------------------------------
@@ -645,72 +654,105 @@ struct WorldGen {
     e.w.wsync();
   }
 
-  // env.py:70-81
-  __device__ __forceinline__ void reset_env(uint64_t* prof = nullptr) {
-    auto stamp = [&](int k) {
-      if (prof && e.w.leader()) prof[k] = e.w.clock();
-    };
-    const Config& c = e.cfg;
-    const Rules& R = e.R;
-    EnvRec* rec = e.rec;
-    int cells = c.W * c.H;
-    int nch = c.nchunk_x * c.nchunk_y;
-    int episode = rec->episode + 1;
-    uint32_t wseed = level_seed(levels, rec->seed_lane, episode);   // env.py:74, of the table's entry where one is set
-    e.w.sync();
-    e.begin_episode(episode);
-    // World.reset engine.py:33-39
-    e.w.block_for(cells, [&](int i) {
-      if (e.objmap) e.objmap[i] = 0;
-      if (e.g_objmap && (const void*)e.g_objmap != (const void*)e.objmap) e.g_objmap[i] = 0;
-    });
+  // ---- the generator's stages ----------------------------------------------------------------------------------------------
+  // Each is written once.  reset_env below runs them back to back in one workgroup (the fused form: Env.reset's kernels, and
+  // gen_body into a pool entry); the world pool's three kernels (gen_bodies.hpp) run them with a pool entry in between.  Every
+  // wave calls a stage.  mark(k): the caller's clock stamp behind the stage's k-th step (phase stamps, probe slots).
+  // World.reset engine.py:33-39: the slot map (where this Env keeps one) and the chunk tables cleared, the creature counts
+  // cleared, the empty record in slot 0, no chunk seen.  No barrier: the caller has one between this and its first World.add.
+  __device__ __forceinline__ void world_reset() {
+    const int cells = e.cfg.W * e.cfg.H, nch = e.cfg.nchunk_x * e.cfg.nchunk_y;
+    if (e.objmap || e.g_objmap)
+      e.w.block_for(cells, [&](int i) {
+        if (e.objmap) e.objmap[i] = 0;
+        if (e.g_objmap && (const void*)e.g_objmap != (const void*)e.objmap) e.g_objmap[i] = 0;
+      });
     e.w.block_for(nch, [&](int i) { e.chunk_seen[i] = 0; e.chunk_order[i] = 0; });
     e.clear_creature_counts();
     if (e.w.wave0()) {
-      init_mt(wseed);
-      e.st(&rec->nchunks_seen, 0);
-      Obj z;
-      z.type = T_NONE; z.health = 0; z.fx = 0; z.fy = 0; z.x = 0; z.y = 0; z.aux = 0; z.pad = 0;
-      e.st(e.objs, z);
+      e.st(&e.rec->nchunks_seen, 0);
+      e.st(e.objs, zero_obj());
     }
-    e.mt_pos = MT_N;
     e.nobj = 1;
     e.dirty_slots = 0;
+  }
+
+  // RandomState(wseed) (env.py:74) into e.mt, unconsumed (mt_pos = MT_N in every wave; wave 0's is the stream's from here on).
+  // No barrier.  Authored worlds (env_worlds.hpp) stop here; the generator goes on with seed_world.
+  __device__ __forceinline__ void seed_stream(uint32_t wseed) {
+    if (e.w.wave0()) init_mt(wseed);
+    e.mt_pos = MT_N;
+    e.rng_invalidate();
+  }
+
+  // The seeding of a generated world: seed_stream, worldgen.py:11 OpenSimplex(seed=randint(0, 2**31 - 1)) -- the world's first
+  // draw --, seed_simplex(that seed, tables).  Ends on a barrier; marks: 0 stream seeded, 1 drawn, 2 permutation in place.
+  template <class M>
+  __device__ __forceinline__ void seed_world(uint32_t wseed, bool tables, M&& mark) {
+    seed_stream(wseed);
     e.w.sync();
-    int px = c.W / 2, py = c.H / 2;
-    if (e.w.wave0()) e.obj_add(T_PLAYER, px, py, 0, 0, 1, 0);  // facing (0, 1) objects.py:72; slot 1
-    e.w.sync();
-    // worldgen.py:11: OpenSimplex(seed=randint(0, 2**31 - 1))
+    mark(0);
     uint32_t sseed = 0;
     if (e.w.wave0()) sseed = e.randint(2147483647u);
     sseed = e.w.bcast_from_wave0(sseed);
-    stamp(9);
-    seed_simplex((int64_t)sseed);
-    stamp(10);
-    // pass 1: classify every cell (parallel over the whole workgroup)
+    mark(1);
+    seed_simplex((int64_t)sseed, tables);
+    mark(2);
+  }
+
+  // The ordered draws, by wave 0 over the classified map: the player into slot 1 (facing (0, 1) objects.py:72; env.py:76 adds it
+  // before generate_world, and no stage before this one calls World.add), then the materials' and the creatures' uniform() chains.
+  // Ends on a barrier with the wave-uniform registers (nobj, mt_pos) in wave 0; marks: 0 window open, 1 materials, 2 creatures.
+  template <class M>
+  __device__ __forceinline__ void draw_world(int cells, M&& mark) {
+    const int px = e.cfg.W / 2, py = e.cfg.H / 2;
+    if (e.w.wave0()) {
+      e.obj_add(T_PLAYER, px, py, 0, 0, 1, 0);
+      window_open();
+      mark(0);
+      resolve_materials(cells);
+      mark(1);
+      place_creatures(cells, px, py);
+      mark(2);
+    }
+    e.w.sync();
+  }
+
+  // strips the generation flags and publishes the material map; ends on a barrier.  Both stores without a test: where the world
+  // was generated in place (g_mat == mat) the second repeats the first, and a test for that in the loop cost the pool's resolve
+  // kernel 3 % of the open loop (profiles/generator_one_tree_ab.txt).
+  __device__ __forceinline__ void strip_flags(int cells) {
+    e.w.block_for(cells, [&](int i) {
+      uint8_t m = (uint8_t)(e.mat[i] & WG_MAT_MASK);
+      e.mat[i] = m;
+      e.g_mat[i] = m;
+    });
+    e.w.sync();
+  }
+
+  // env.py:70-81, the fused form: the stages in order.  prof: the env's stamp row (9 .. 13) or null.
+  __device__ __forceinline__ void reset_env(uint64_t* prof = nullptr) {
+    auto stamp = [&](int k) { if (prof && e.w.leader()) prof[k] = e.w.clock(); };
+    const Config& c = e.cfg;
+    const int cells = c.W * c.H;
+    const int episode = e.rec->episode + 1;
+    const uint32_t wseed = level_seed(levels, e.rec->seed_lane, episode);   // env.py:74, of the table's entry where one is set
+    e.w.sync();
+    e.begin_episode(episode);
+    world_reset();
+    seed_world(wseed, true, [&](int k) { if (k > 0) stamp(8 + k); });   // 9, 10
+    // classify every cell (parallel over the whole workgroup)
     Simplex<W> sx{perm, pg3, tab};
     const ClassIds ids = class_ids();
+    const int px = c.W / 2, py = c.H / 2;
     e.w.block_for(cells, [&](int i) {
       int x = i / c.H, y = i - x * c.H;
       e.mat[i] = classify(sx, ids, x, y, px, py);
     });
     e.w.sync();
     stamp(11);
-    if (e.w.wave0()) {
-      window_open();
-      resolve_materials(cells);
-      stamp(12);
-      place_creatures(cells, px, py);
-      stamp(13);
-    }
-    e.w.sync();
-    // strip the generation flags, publish the material map
-    e.w.block_for(cells, [&](int i) {
-      uint8_t m = e.mat[i] & WG_MAT_MASK;
-      e.mat[i] = m;
-      if (e.g_mat != e.mat) e.g_mat[i] = m;
-    });
-    e.w.sync();
+    draw_world(cells, [&](int k) { if (k > 0) stamp(11 + k); });   // 12, 13
+    strip_flags(cells);
   }
 };
 

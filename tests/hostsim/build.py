@@ -28,8 +28,9 @@ SAN_FLAGS = ['-O1', '-fno-omit-frame-pointer', '-fsanitize=address,undefined', '
 # target -> its source; a new entry point is one row here
 LIBS = {'hostsim': 'hostsim.cpp', 'symbolic': 'symbolic_host.cpp', 'final': 'final_host.cpp', 'levels': 'levels_host.cpp',
         'subset': 'subset_host.cpp', 'rollout_envs': 'rollout_envs_host.cpp', 'levelset': 'levelset_host.cpp',
-        'worlds': 'worlds_host.cpp', 'legal': 'legal_host.cpp'}
-PROGRAMS = {'final_main': 'final_main.cpp', 'worlds_main': 'worlds_main.cpp', 'legal_main': 'legal_main.cpp'}
+        'worlds': 'worlds_host.cpp', 'legal': 'legal_host.cpp', 'generator_forms': 'generator_forms_host.cpp'}
+PROGRAMS = {'final_main': 'final_main.cpp', 'worlds_main': 'worlds_main.cpp', 'legal_main': 'legal_main.cpp',
+            'generator_forms_main': 'generator_forms_main.cpp'}
 
 _libs = {}
 
