@@ -7,8 +7,8 @@ from .batched import BatchedEnv, CrafterDeviceError  # noqa: F401
 from .env import Env  # noqa: F401
 from .lib import CrafterLibError  # noqa: F401
 from .abi import (FP_ALL, FP_CHUNKS, FP_CLOCK, FP_DYNAMICS, FP_IDENT, FP_MAP, FP_OBJECTS, FP_PARTS, FP_PLAYER, FP_RNG,  # noqa: F401
-                  FP_VISIBLE)
-from .state import fingerprint_host, levels_pick  # noqa: F401
+                  FP_VISIBLE, NAV_MAX_TARGETS)
+from .state import fingerprint_host, levels_pick, navigate_host  # noqa: F401
 from .worlds import WorldBank  # noqa: F401
 from .recorder import BatchedEpisodeRecorder, BatchedStatsRecorder, EnvStatsRecorder  # noqa: F401
 from .vec import VecEnvView  # noqa: F401

@@ -48,6 +48,8 @@ FP_DYNAMICS = FP_VISIBLE | FP_CLOCK | FP_RNG | FP_CHUNKS
 FP_ALL = FP_DYNAMICS | FP_IDENT
 FP_NAMES = ('map', 'objects', 'player', 'clock', 'rng', 'chunks', 'ident')
 
+NAV_MAX_TARGETS = 16   # target sets per navigation query (crafter_hip_navigate.h CRAFTER_NAV_MAX_TARGETS)
+
 # texture slots of TablePtrs.tex_tile (crafter_hip_types.h CRAFTER_TEX_*)
 TEX_MATERIAL0 = 0
 (TEX_PLAYER_LEFT, TEX_PLAYER_RIGHT, TEX_PLAYER_UP, TEX_PLAYER_DOWN, TEX_PLAYER_SLEEP, TEX_COW,

@@ -894,6 +894,83 @@ class BatchedEnv:
     self._fingerprint(0, mask, None, out)
     return out
 
+  # ------------------------------------------------------------------ navigation queries (include/crafter_hip_navigate.h)
+  @staticmethod
+  def _class_set(names, entry, what):
+    """One entry of `targets` / `passable` -- a name of `names`, an id, or a list of either -- as a bit set over the ids
+    1 .. len(names) - 1 (id 0, 'none', is no cell's class).  ValueError for anything else, and for an empty set."""
+    items = list(entry) if isinstance(entry, (list, tuple, set, frozenset)) else [entry]
+    bits = 0
+    for item in items:
+      if isinstance(item, str):
+        if item not in names[1:]:
+          raise ValueError(f'{what}: unknown name {item!r} (one of {names[1:]})')
+        c = names.index(item, 1)
+      elif isinstance(item, (int, np.integer)) and not isinstance(item, bool):
+        c = int(item)
+        if not 1 <= c < len(names):
+          raise ValueError(f'{what}: id {c} outside 1 .. {len(names) - 1}')
+      else:
+        raise ValueError(f'{what}: {item!r} is neither a name nor an id')
+      bits |= 1 << c
+    if not bits:
+      raise ValueError(f'{what}: an empty set')
+    return bits
+
+  @staticmethod
+  def _check_targets(class_names, n_materials, walkable, targets, passable=None):
+    """The host side of navigate(), callable without a device: -> (the K target class sets, the passable material set) as
+    ints.  class_names: symbolic_names['classes']; walkable: the rules' walkable list, the default of `passable`.  ValueError
+    before anything is enqueued: K outside 1 .. NAV_MAX_TARGETS, an unknown name, 'none' / id 0, an id beyond the classes
+    (the materials, for `passable`), an empty set, more than 31 classes."""
+    names = list(class_names)
+    if len(names) > 31:
+      raise ValueError(f'navigate() holds a class set in 32 bits: {len(names)} classes are too many')
+    if isinstance(targets, (str, int, np.integer)) or not hasattr(targets, '__len__'):
+      raise ValueError('targets must be a sequence of names, ids or lists of them (one entry per query)')
+    if not 1 <= len(targets) <= abi.NAV_MAX_TARGETS:
+      raise ValueError(f'targets must have 1 .. {abi.NAV_MAX_TARGETS} entries, not {len(targets)}')
+    sets = [BatchedEnv._class_set(names, t, f'targets[{k}]') for k, t in enumerate(targets)]
+    walk = BatchedEnv._class_set(names[:n_materials + 1], list(walkable) if passable is None else passable, 'passable')
+    return sets, walk
+
+  def class_mask(self, names_or_ids):
+    """The 32-bit class set navigate() takes for a name of symbolic_names['classes'], a class id, or a list of either."""
+    return self._class_set(self.symbolic_names['classes'], names_or_ids, 'class_mask')
+
+  def navigate(self, targets, passable=None, mask=None, out=None):
+    """(dist int32 [N, K], first int32 [N, K], facing uint8 [N, K]) on the device: for each env and each of the K entries of
+    `targets`, how far on foot the nearest cell of that kind is and which move comes first.  An entry is a class name of
+    symbolic_names['classes'] ('tree', 'water', 'cow', ...), a class id, or a list of either (a set: ['coal', 'iron']);
+    passable: names or ids of the materials one walks on (default: the rules' `walkable` -- grass, sand, path --, what a plain
+    object walks on, objects.py:44-47; the player's own set adds 'lava').  A cell counts as a target by what info['semantic']
+    shows on it -- the object standing there, else the material --, the player's own cell never; one walks over passable cells
+    that hold no object.  dist: the number of move actions after which the player faces the target (or stands on it, if it is
+    passable and free) provided nothing else moves, -1 if no walk exists; always >= 1 otherwise.  first: the index in
+    action_names of the first move of a shortest walk -- of left, right, up, down the first that shortens it --, -1 where dist
+    is -1.  facing: 1 iff the cell in front of the player is a target ("`do` now").  The query ignores sleeping, damage and
+    what creatures will do next.  After a step() that auto-reset an env the row describes the new episode's first state, after
+    a rollout() the state behind its last step.  Read-only: no draw from the envs' RNG, no byte of state changes.  mask: rows
+    with a zero byte are left untouched.  out = (dist, first, facing): contiguous device tensors of exactly those dtypes and
+    shapes to write into.  Bad targets raise ValueError before anything is enqueued."""
+    fn = _libmod.require(self._lib, 'crafter_navigate', 'navigate()')
+    sets, walk = self._check_targets(self.symbolic_names['classes'], len(self.rules['materials']), self.rules['walkable'], targets, passable)
+    K = len(sets)
+    dtypes = (torch.int32, torch.int32, torch.uint8)
+    if out is None:
+      out = tuple(torch.zeros((self.num_envs, K), dtype=dt, device=self.device) for dt in dtypes)
+    else:
+      if len(out) != 3:
+        raise ValueError('out must be a triple (dist, first, facing)')
+      for k, (t, dt) in enumerate(zip(out, dtypes)):
+        self._out(t, (self.num_envs, K), dt, f'out[{k}]')
+    mask, mptr = self._mask(mask, check_len=True)
+    host = (C.c_uint32 * K)(*sets)   # read before the call returns
+    dist, first, facing = out
+    self._call(fn, mptr, C.cast(host, C.c_void_p), K, walk, _ptr(dist), _ptr(first), _ptr(facing))
+    self._keep = mask
+    return dist, first, facing
+
   def info(self):
     """Device-tensor views of what the reference puts into ``info`` (env.py:108-115)."""
     o, r = self._off, self._rec_i32

@@ -20,6 +20,7 @@
 
 #include "../../include/crafter_hip.h"
 #include "../../include/crafter_hip_fingerprint.h"
+#include "../../include/crafter_hip_navigate.h"
 #include "crafter_rollout.hpp"
 #include "crafter_rollout_subset.hpp"
 #include "crafter_subset.hpp"
@@ -31,6 +32,7 @@
 #include "fingerprint.hpp"
 #include "launch_plan.hpp"
 #include "legal.hpp"
+#include "navigate.hpp"
 #include "symbolic.hpp"
 #include "wave_gfx950.hpp"
 
@@ -269,6 +271,7 @@ int crafter_upload_tables(crafter_handle* h, const crafter_host_tables* t) {
     tb.render_static = (const uint8_t*)it->second.ptr;
   }
   h->plan = launch_plan(c, default_rules, h->lds_pad, h->rollout_lds_pad);   // the rules are known: the instance may be a compiled-in one
+  h->n_materials = r->n_materials;
   h->have_tables = true;
   return 0;
 }
@@ -918,6 +921,41 @@ int crafter_fingerprint(crafter_handle* h, const uint8_t* mask, uint32_t parts, 
   const dim3 grid((unsigned)((h->cfg.num_envs + kFingerprintEnvs - 1) / kFingerprintEnvs)), block(kFingerprintThreads);
   hipLaunchKernelGGL(crafter_fingerprint_kernel, grid, block, 0, s, h->cfg, h->tb, h->st, mask, parts, key, part_hash);
   return launched(h, "crafter_fingerprint launch");
+}
+
+// The navigation query of the envs as they stand on `stream` (navigate.hpp).  Like crafter_symbolic it reads live rows only and
+// waits for no batch of the pool.  The instance follows the handle's config: boards in registers for worlds of at most 64 x 64
+// cells, in LDS beyond; the object path as crafter_legal_actions.
+int crafter_navigate(crafter_handle* h, const uint8_t* mask, const uint32_t* targets, int32_t k, uint32_t passable,
+                     int32_t* dist, int32_t* first, uint8_t* facing, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  if (ready(h, "crafter_navigate")) return 1;
+  if (const int why = nav_check(h->n_materials, targets, k, passable)) return fail(h, std::string("crafter_navigate: ") + nav_error_text(why));
+  if (!dist || !first) return fail(h, "crafter_navigate: dist or first is null");
+  NavQuery q;
+  memset(&q, 0, sizeof(q));
+  memcpy(q.targets, targets, sizeof(uint32_t) * (size_t)k);
+  q.passable = passable;
+  q.k = k;
+  const bool map = !h->plan.maps_in_lds;
+  if (nav_in_registers(h->cfg)) {
+    if (adopt_stream(h, s)) return 1;
+    const dim3 grid((unsigned)((h->cfg.num_envs + kNavEnvs - 1) / kNavEnvs)), block(kNavThreads);
+    if (map)
+      hipLaunchKernelGGL(crafter_navigate_kernel<1>, grid, block, 0, s, h->cfg, h->tb, h->st, mask, q, dist, first, facing);
+    else
+      hipLaunchKernelGGL(crafter_navigate_kernel<0>, grid, block, 0, s, h->cfg, h->tb, h->st, mask, q, dist, first, facing);
+  } else {
+    const size_t lds = nav_lds_bytes(h->cfg);
+    if (lds > (size_t)kNavMaxLds) return fail(h, "crafter_navigate: the area's boards exceed 64 KiB of LDS");
+    if (adopt_stream(h, s)) return 1;
+    const dim3 grid((unsigned)h->cfg.num_envs), block(kNavWideThreads);
+    if (map)
+      hipLaunchKernelGGL(crafter_navigate_lds_kernel<1>, grid, block, lds, s, h->cfg, h->tb, h->st, mask, q, dist, first, facing);
+    else
+      hipLaunchKernelGGL(crafter_navigate_lds_kernel<0>, grid, block, lds, s, h->cfg, h->tb, h->st, mask, q, dist, first, facing);
+  }
+  return launched(h, "crafter_navigate launch");
 }
 
 #ifdef CRAFTER_PROBES

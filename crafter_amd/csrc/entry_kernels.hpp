@@ -382,6 +382,31 @@ crafter_fingerprint_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t
   fingerprint_body<WF>(w, (int)blockIdx.x * kFingerprintEnvs + wave, cfg, tb, st, mask, parts, key, part_hash);
 }
 
+// crafter_navigate (navigate.hpp), worlds of at most 64 x 64 cells: one wave per env, kNavEnvs envs per workgroup, each wave with
+// its own staging strip and no barrier: the waves of the batch tail and of masked rows leave at once.  MAP as for
+// crafter_symbolic_kernel.  The query travels by value.  (Eight waves per SIMD, asked for: the query's words and the sweep's masks
+// would otherwise take a few scalar registers more than that allows.)
+template <int MAP>
+__global__ void __launch_bounds__(kNavThreads, 8)
+crafter_navigate_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, NavQuery q,
+                        int32_t* __restrict__ dist, int32_t* __restrict__ first, uint8_t* __restrict__ facing) {
+  __shared__ uint32_t strips[kNavEnvs][kNavStripWords];
+  typedef WaveGfx950<kNavThreads> WN;
+  WN w;
+  const int wave = WN::uni((int)(threadIdx.x >> 6));
+  navigate_body<WN, MAP>(w, strips[wave], (int)blockIdx.x * kNavEnvs + wave, cfg, tb, st, mask, q, dist, first, facing);
+}
+
+// ... and any other area: one workgroup per env, the boards in nav_lds_bytes(cfg) of LDS.
+template <int MAP>
+__global__ void __launch_bounds__(kNavWideThreads)
+crafter_navigate_lds_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, NavQuery q,
+                            int32_t* __restrict__ dist, int32_t* __restrict__ first, uint8_t* __restrict__ facing) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  WaveGfx950<kNavWideThreads> w;
+  navigate_lds_body<WaveGfx950<kNavWideThreads>, MAP>(w, (uint32_t*)smem, (int)blockIdx.x, cfg, tb, st, mask, q, dist, first, facing);
+}
+
 // crafter_reseed (env_levels.hpp): one thread per env edits its record and empties its two pool entries.
 __global__ void __launch_bounds__(kReseedThreads)
 crafter_reseed_kernel(Config cfg, StatePtrs st, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_lane,

@@ -217,6 +217,11 @@ class Env(BaseClass):
     """BatchedEnv.legal_actions() for this env: bool [n_actions], True where the action passes its guards in the current state."""
     return self._batch.legal_actions()[0].cpu().numpy().astype(bool)
 
+  def navigate(self, targets, passable=None):
+    """BatchedEnv.navigate(targets, passable) for this env: (dist int32 [K], first int32 [K], facing bool [K]) as numpy arrays."""
+    dist, first, facing = self._batch.navigate(targets, passable)
+    return dist[0].cpu().numpy(), first[0].cpu().numpy(), facing[0].cpu().numpy().astype(bool)
+
   def fingerprint(self, parts=abi.FP_DYNAMICS):
     """BatchedEnv.fingerprint(parts) for this env: the key as an unsigned Python int."""
     return int(self._batch.fingerprint(parts)[0].item()) & 0xFFFFFFFFFFFFFFFF

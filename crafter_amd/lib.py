@@ -81,6 +81,7 @@ EXPORTS = list(SIGNATURES)
 # of their own, looked up by name.  Always optional: a library without one loads, and require() says what is missing.
 EXTENSIONS = {
     'crafter_fingerprint': ('crafter_hip_fingerprint.h', i32, [vp, vp, C.c_uint32, vp, vp, vp]),
+    'crafter_navigate': ('crafter_hip_navigate.h', i32, [vp, vp, vp, i32, C.c_uint32, vp, vp, vp, vp]),
 }
 
 _lib = None

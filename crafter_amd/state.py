@@ -162,6 +162,60 @@ def fingerprint_host(snapshot, seed_lane, parts=abi.FP_ALL):
   return fingerprint_combine(hashes, parts), hashes
 
 
+def navigate_host(snapshot, n_materials, targets, passable, move_actions):
+  """The Python mirror of the device's navigation query (include/crafter_hip_navigate.h) over a snapshot() dict --
+  BatchedEnv.snapshot(i) or OracleEnv.snapshot() -> (dist int32 [K], first int32 [K], facing bool [K]).  n_materials: the rules'
+  material count (object class ids start behind it); targets: K class sets as ints (bit c = class c); passable: a set of
+  material ids as an int; move_actions: the action indices of move left, right, up, down.  Written unlike the kernel on
+  purpose: a queue-based breadth-first search that stores an integer distance per cell, then the rule for `first` over the
+  four neighbours."""
+  import collections
+  mat = np.asarray(snapshot['mat'])
+  W, H = mat.shape
+  cls = mat.astype(np.int64).copy()
+  free = np.zeros((W, H), bool)
+  for m in range(1, n_materials + 1):
+    if passable >> m & 1:
+      free |= mat == m
+  player = None
+  for tp, x, y, _, fx, fy, _ in snapshot['objects']:
+    cls[x, y] = n_materials + tp
+    free[x, y] = False
+    if tp == abi.T_PLAYER and player is None:
+      player = (x, y, fx, fy)
+  px, py, fx, fy = player
+  free[px, py] = True
+  steps = ((-1, 0), (1, 0), (0, -1), (0, 1))
+  inside = lambda x, y: 0 <= x < W and 0 <= y < H
+  K = len(targets)
+  dist, first, facing = np.full(K, -1, np.int32), np.full(K, -1, np.int32), np.zeros(K, bool)
+  for k, target in enumerate(targets):
+    is_target = (int(target) >> cls & 1).astype(bool)
+    is_target[px, py] = False
+    d = np.full((W, H), -1, np.int64)
+    queue = collections.deque()
+    for x, y in zip(*np.nonzero(is_target)):
+      d[x, y] = 0
+      queue.append((int(x), int(y)))
+    while queue:
+      x, y = queue.popleft()
+      for dx, dy in steps:
+        nx, ny = x + dx, y + dy
+        if inside(nx, ny) and d[nx, ny] < 0 and free[nx, ny]:   # (a target cell has its 0 already)
+          d[nx, ny] = d[x, y] + 1
+          queue.append((nx, ny))
+    facing[k] = inside(px + fx, py + fy) and bool(is_target[px + fx, py + fy])
+    if d[px, py] < 0:
+      continue
+    dist[k] = d[px, py]
+    for a, (dx, dy) in zip(move_actions, steps):
+      nx, ny = px + dx, py + dy
+      if inside(nx, ny) and d[nx, ny] == d[px, py] - 1:   # (d >= 0: the cell is a target or free)
+        first[k] = a
+        break
+  return dist, first, facing
+
+
 def levels_cum(weights):
   """K weights (non-negative, not all zero) -> cum uint32 [K], cum[j] = min(floor(2^32 * sum(w[:j + 1]) / sum(w)), 2^32 - 1),
   in exact rational arithmetic."""
