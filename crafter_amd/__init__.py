@@ -10,6 +10,7 @@ from .abi import (FP_ALL, FP_CHUNKS, FP_CLOCK, FP_DYNAMICS, FP_IDENT, FP_MAP, FP
                   FP_VISIBLE, NAV_MAX_TARGETS)
 from .state import fingerprint_host, levels_pick, navigate_host  # noqa: F401
 from .worlds import WorldBank  # noqa: F401
+from . import edits  # noqa: F401
 from .recorder import BatchedEpisodeRecorder, BatchedStatsRecorder, EnvStatsRecorder  # noqa: F401
 from .vec import VecEnvView  # noqa: F401
 

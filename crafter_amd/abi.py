@@ -39,6 +39,18 @@ ALL_STATUS_NAMES = dict(STATUS_NAMES)
 ALL_STATUS_NAMES[STATUS_BAD_WORLD] = (
     'ST_BAD_WORLD: reset(worlds=...) met a world it had to repair (a material id, an object record or a facing out of range; '
     'the record was skipped / the value replaced) or a world id outside the bank (that env was left as it was)')
+STATUS_BAD_EDIT = 256    # CRAFTER_ST_BAD_EDIT (include/crafter_hip_edit.h, beside crafter_edit_envs)
+ALL_STATUS_NAMES[STATUS_BAD_EDIT] = (
+    'ST_BAD_EDIT: edit() met an op it had to skip or repair (an unknown kind, a cell outside the map, a material, item, field or '
+    'clock value out of range, an occupied or empty cell, the player where an object is meant); the tape\'s other ops were applied')
+
+# an edit op (crafter_hip_edit.h): CRAFTER_EDIT_WORDS int32 words, the kind first
+EDIT_WORDS = 8
+(EDIT_NOP, EDIT_SET_CELL, EDIT_ADD, EDIT_REMOVE, EDIT_MOVE, EDIT_SET_OBJECT, EDIT_SET_ITEM, EDIT_SET_PLAYER, EDIT_SET_CLOCK,
+ EDIT_KINDS) = range(10)
+EDIT_HEALTH, EDIT_FACING, EDIT_AUX = 1, 2, 4                      # SET_OBJECT's `which`
+EDIT_FIELDS = ('sleeping', 'hunger2', 'thirst2', 'fatigue2', 'recover2')   # SET_PLAYER's `field`, by index
+EDIT_FIELD_RANGE = {'sleeping': (0, 1), 'hunger2': (0, 50), 'thirst2': (0, 40), 'fatigue2': (-20, 60), 'recover2': (-30, 50)}
 
 # parts of a state fingerprint (crafter_hip_types.h CRAFTER_FP_*): bit p of a part mask, column p of fingerprint_parts()
 FP_PARTS = 7

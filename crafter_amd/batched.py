@@ -767,6 +767,42 @@ class BatchedEnv:
       self._keep = (i, actions, o, r, d)
     return o, r, d
 
+  # ------------------------------------------------------------------ edits in place (include/crafter_hip_edit.h)
+  def edit(self, idx, ops):
+    """Edits the envs idx names in place, between two steps (crafter_edit_envs): cells, objects, the inventory, the player's
+    counters and the clock, with every derived table -- slot map, census, chunk order -- following as in a step.  idx: n env
+    indices, none twice.  ops: one tape (a list of crafter_amd.edits ops: set_cell, add, remove, move, set_object, set_item,
+    set_player, set_clock) applied to every named env, or a list of n tapes, or an int32 device tensor [n, L, 8] in the
+    encoding of edits.encode() (padded with NOP), which is not read back: a loop can build its tapes with torch and never leave
+    the device.  Each op means what the reference statement it is named after means between two Env.step calls; an edit draws
+    nothing from the env's RNG, leaves obs / reward / done / info['semantic'] as they are (render() shows an edit at once) and
+    neither reads nor writes any other row; the edited episode ends and auto-resets like any other.
+    Host tapes are checked by edits.encode() and raise ValueError before anything is enqueued; what only the state can tell
+    (an occupied cell, no object where one is meant) and everything in a device tensor is checked on the device: such an op is
+    skipped or repaired, the tape's other ops are applied and check_errors() raises (ST_BAD_EDIT).  idx is checked as for
+    step_envs().  An empty idx enqueues nothing."""
+    from . import edits as _edits
+    fn = _libmod.require(self._lib, 'crafter_edit_envs', 'edit()')
+    i, _ = self._index(idx, self.num_envs, 'idx', unique=True)
+    n = int(i.numel())
+    if n > self.num_envs:
+      raise ValueError(f'idx names {n} envs, the batch has {self.num_envs}')
+    if _on_device(ops):
+      if ops.device != self.device:
+        raise ValueError(f'ops on {ops.device}, batch on {self.device}')
+      if ops.dtype != torch.int32 or ops.dim() != 3 or ops.shape[0] != n or ops.shape[1] < 1 or ops.shape[2] != _edits.WORDS:
+        raise ValueError(f'a device tape is int32 [{n}, L, {_edits.WORDS}] with L >= 1 (idx names {n} envs)')
+      tape = ops.contiguous()
+      if tape.data_ptr() % 16:
+        tape = tape.clone()
+    else:
+      tape = torch.from_numpy(_edits.encode(self, ops, n)).to(self.device)
+    if n:
+      self._call(fn, _ptr(i), n, _ptr(tape), int(tape.shape[1]))
+      self._keep = (i, tape)
+      if self._unbounded:   # a clock op may have set a step beyond any this batch ran: the next _grow_daylight reads the counters
+        self._step_bound = self.cfg.n_daylight
+
   def _render_handle(self, size):
     """A second handle with another frame size over the SAME state buffers: Env.render(size)
     (env.py:120-130; the reference's VideoRecorder asks for 512x512, recorder.py:92)."""

@@ -22,7 +22,7 @@ UNITS = [(SRC.name, []), (SRC_ROLLOUT.name, ROLLOUT_FLAGS), (SRC_SUBSET.name, []
 
 def sources():
   return ([ROOT / 'csrc' / name for name, _ in UNITS] + sorted((ROOT / 'csrc').glob('*.hpp')) + sorted((ROOT / 'csrc').glob('*.inc')) +
-          [ROOT.parent / 'include' / name for name in ('crafter_hip.h', 'crafter_hip_types.h', 'crafter_hip_fingerprint.h', 'crafter_hip_navigate.h')])
+          [ROOT.parent / 'include' / name for name in ('crafter_hip.h', 'crafter_hip_types.h', 'crafter_hip_fingerprint.h', 'crafter_hip_navigate.h', 'crafter_hip_edit.h')])
 
 
 def source_hash():
@@ -112,7 +112,8 @@ def _compile_resource_usage():
       cur = out.setdefault(key, {})
       continue
     for key, pat in (('vgprs', r'VGPRs: (\d+)'), ('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'),
-                     ('occupancy', r'Occupancy \[waves/SIMD\]: (\d+)'), ('vgpr_spill', r'VGPRs Spill: (\d+)')):
+                     ('occupancy', r'Occupancy \[waves/SIMD\]: (\d+)'), ('vgpr_spill', r'VGPRs Spill: (\d+)'),
+                     ('sgprs', r'TotalSGPRs: (\d+)'), ('sgpr_spill', r'SGPRs Spill: (\d+)')):
       m = re.search(pat, line)
       if m and cur is not None:
         cur[key] = int(m.group(1))

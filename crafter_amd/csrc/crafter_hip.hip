@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/crafter_hip.h"
+#include "../../include/crafter_hip_edit.h"
 #include "../../include/crafter_hip_fingerprint.h"
 #include "../../include/crafter_hip_navigate.h"
 #include "crafter_rollout.hpp"
@@ -26,6 +27,7 @@
 #include "crafter_subset.hpp"
 #include "dispatch_order.hpp"
 #include "env_copy.hpp"
+#include "env_edit.hpp"
 #include "env_kernels.hpp"
 #include "env_levels.hpp"
 #include "env_worlds.hpp"
@@ -956,6 +958,33 @@ int crafter_navigate(crafter_handle* h, const uint8_t* mask, const uint32_t* tar
       hipLaunchKernelGGL(crafter_navigate_lds_kernel<0>, grid, block, lds, s, h->cfg, h->tb, h->st, mask, q, dist, first, facing);
   }
   return launched(h, "crafter_navigate launch");
+}
+
+// Edits of the n envs idx names, in place (env_edit.hpp): the index check of crafter_step_n_envs, then one workgroup per named
+// env that replays its row of the tape.  Like crafter_save_envs it touches live rows only -- the pool's side streams never write
+// them, and an edit leaves the pool's entries alone -- so it waits for no batch.  An ordered handle's next_step entries of the
+// named envs follow a clock edit (the dispatch order's hint: stale it would cost time, never correctness).
+int crafter_edit_envs(crafter_handle* h, const int32_t* idx, int32_t n, const int32_t* ops, int32_t ops_per_env, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  if (ready(h, "crafter_edit_envs")) return 1;
+  if (n < 0 || n > h->cfg.num_envs) return fail(h, "crafter_edit_envs: n outside 0 .. num_envs");
+  if (n == 0) return 0;
+  if (!idx) return fail(h, "crafter_edit_envs: null index list");
+  if (!ops) return fail(h, "crafter_edit_envs: null ops");
+  if (ops_per_env < 1) return fail(h, "crafter_edit_envs: ops_per_env must be at least 1");
+  if (((uintptr_t)ops & 15u) != 0) return fail(h, "crafter_edit_envs: ops must be 16-byte aligned");
+  const int lds = edit_layout(h->cfg).total;   // (<= plan.render_lds: beyond 64 KB crafter_create has allowed the kernel that much, big_lds_kernels)
+  if (adopt_stream(h, s)) return 1;
+  if (need_scratch(h, (void**)&h->rollout_row_of, (size_t)h->cfg.num_envs * sizeof(int32_t), "crafter_edit_envs: row scratch")) return 1;
+  RolloutEnvsCheck chk;
+  chk.idx = idx; chk.n = n;
+  if (index_check_scratch(h, "crafter_edit_envs", s, &chk.stamp)) return 1;
+  chk.mark = h->copy_mark; chk.verdict = h->copy_verdict; chk.rec = (EnvRec*)h->st.rec; chk.rows = h->cfg.num_envs;
+  chk.row_of = h->rollout_row_of;
+  launch_rollout_envs_check(chk, s, nullptr, nullptr);
+  hipLaunchKernelGGL(crafter_edit_envs_kernel, dim3((unsigned)n), dim3(kEditThreads), lds, s, h->cfg, h->tb, h->st, idx,
+                     (const int32_t*)h->copy_verdict, ops, (int)ops_per_env, h->next_step);
+  return launched(h, "crafter_edit_envs launch");
 }
 
 #ifdef CRAFTER_PROBES

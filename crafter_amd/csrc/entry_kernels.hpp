@@ -407,6 +407,18 @@ crafter_navigate_lds_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_
   navigate_lds_body<WaveGfx950<kNavWideThreads>, MAP>(w, (uint32_t*)smem, (int)blockIdx.x, cfg, tb, st, mask, q, dist, first, facing);
 }
 
+// crafter_edit_envs (env_edit.hpp): one workgroup per named env, behind the index check of crafter_step_n_envs (a refused list:
+// every workgroup leaves at once, no row changes).  Workgroup b replays row b of the tape on env idx[b].
+__global__ void __launch_bounds__(kEditThreads)
+crafter_edit_envs_kernel(Config cfg, TablePtrs tb, StatePtrs st, const int32_t* __restrict__ idx, const int32_t* __restrict__ verdict,
+                         const int32_t* __restrict__ ops, int ops_per_env, int32_t* __restrict__ next_step) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int env = step_envs_env(idx, verdict, (int)blockIdx.x);
+  if (env < 0) return;
+  WaveGfx950<kEditThreads> w;
+  edit_body(w, smem, env, cfg, tb, st, ops + (size_t)blockIdx.x * (size_t)ops_per_env * kEditWords, ops_per_env, next_step);
+}
+
 // crafter_reseed (env_levels.hpp): one thread per env edits its record and empties its two pool entries.
 __global__ void __launch_bounds__(kReseedThreads)
 crafter_reseed_kernel(Config cfg, StatePtrs st, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_lane,

@@ -209,7 +209,7 @@ static std::vector<const void*> big_lds_kernels() {
 #undef CRAFTER_X
   for (const void* f : {(const void*)crafter_reset_kernel, (const void*)crafter_reset_worlds_kernel, (const void*)crafter_gen_resolve_kernel<0>,
                         (const void*)crafter_requeue_reset_kernel, (const void*)crafter_requeue_final_kernel,
-                        (const void*)crafter_render_kernel})
+                        (const void*)crafter_render_kernel, (const void*)crafter_edit_envs_kernel})
     big.push_back(f);
   return big;
 }

@@ -186,6 +186,30 @@ __host__ __device__ inline LdsLayout big_reset_layout(const Config& c) {
   return L;
 }
 
+// crafter_edit_envs (env_edit.hpp): the env's tables where big_reset_layout keeps them -- an LDS-resident world's maps and slot
+// table staged, a large world's left where they live -- and nothing else: an edit neither generates nor draws, so no worldgen
+// scratch, no pixel buffer and no renderer region.  20,352 B for the default geometry, 14,272 B for 256x256.
+__host__ __device__ inline LdsLayout edit_layout(const Config& c) {
+  LdsLayout L = lds_layout(c);   // (for maps_in_lds: the one decision every kernel over the same state shares)
+  int cells = c.W * c.H;
+  int o = 0;
+  L.frame = 0;
+  L.frame_bytes = 0;
+  L.frame_over_objs = 0;
+  L.wg = L.mtb = -1;
+  if (L.maps_in_lds) {
+    L.mat = o;        o += align16(cells);
+    L.objmap = o;     o += align16(2 * cells);
+    L.objs = o;       o += 16 * c.max_objects;
+  } else {
+    L.mat = L.objmap = -1;
+    L.objs = -1;
+  }
+  layout_tail(L, o, c, CRAFTER_RULES_HEAD_BYTES, true);
+  layout_end(L, o, 0);
+  return L;
+}
+
 // LDS of the frame kernel: record | MT state | second MT state | frame record | night pixel buffer | renderer region
 struct FrameLayout {
   int rec, mt, mtb, cells, pix, pix_bytes, scratch, render, total;

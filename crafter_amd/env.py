@@ -198,6 +198,17 @@ class Env(BaseClass):
     w = self._batch.export_worlds([0])
     return dict(mat=w['mat'][0], objects=w['objects'][0], inventory=w['inventory'][0])
 
+  def edit(self, ops):
+    """BatchedEnv.edit for this env: ops is one tape of crafter_amd.edits ops (set_cell, add, remove, move, set_object,
+    set_item, set_player, set_clock), applied in order to the episode under way -- `env._world[x, y] = ...`,
+    `env._world.add(...)`, `env._player.inventory[...] = ...` of the reference.  render() shows the result at once; an op the
+    device had to refuse raises CrafterDeviceError (ST_BAD_EDIT) with the tape's other ops applied."""
+    self._batch.edit([0], list(ops))
+    try:
+      self._batch.check_errors()
+    finally:   # (a clock op moves it -- also in a tape with a refused op: the other ops were applied)
+      self._step = int(self._batch.records()[0]['step'])
+
   def render(self, size=None):
     size = None if size is None else tuple(int(v) for v in (size if hasattr(size, '__len__') else (size, size)))
     return self._batch.render(size)[0].cpu().numpy()

@@ -82,6 +82,7 @@ EXPORTS = list(SIGNATURES)
 EXTENSIONS = {
     'crafter_fingerprint': ('crafter_hip_fingerprint.h', i32, [vp, vp, C.c_uint32, vp, vp, vp]),
     'crafter_navigate': ('crafter_hip_navigate.h', i32, [vp, vp, vp, i32, C.c_uint32, vp, vp, vp, vp]),
+    'crafter_edit_envs': ('crafter_hip_edit.h', i32, [vp, vp, i32, vp, i32, vp]),
 }
 
 _lib = None
