@@ -8,7 +8,8 @@ from .env import Env  # noqa: F401
 from .lib import CrafterLibError  # noqa: F401
 from .abi import (FP_ALL, FP_CHUNKS, FP_CLOCK, FP_DYNAMICS, FP_IDENT, FP_MAP, FP_OBJECTS, FP_PARTS, FP_PLAYER, FP_RNG,  # noqa: F401
                   FP_VISIBLE, NAV_MAX_TARGETS)
-from .state import fingerprint_host, levels_pick, navigate_host  # noqa: F401
+from .abi import AUDIT_NAMES  # noqa: F401
+from .state import audit_host, fingerprint_host, levels_pick, navigate_host  # noqa: F401
 from .worlds import WorldBank  # noqa: F401
 from . import edits  # noqa: F401
 from .recorder import BatchedEpisodeRecorder, BatchedStatsRecorder, EnvStatsRecorder  # noqa: F401

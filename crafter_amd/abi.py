@@ -60,7 +60,13 @@ FP_DYNAMICS = FP_VISIBLE | FP_CLOCK | FP_RNG | FP_CHUNKS
 FP_ALL = FP_DYNAMICS | FP_IDENT
 FP_NAMES = ('map', 'objects', 'player', 'clock', 'rng', 'chunks', 'ident')
 
-NAV_MAX_TARGETS = 16   # target sets per navigation query (crafter_hip_navigate.h CRAFTER_NAV_MAX_TARGETS)
+# the invariants of an env row (crafter_hip_audit.h CRAFTER_AUDIT_*): bit b of audit()'s flags, AUDIT_NAMES[b] its name
+AUDIT_BITS = 11
+(AUDIT_NOT_RESET, AUDIT_REC, AUDIT_PLAYER, AUDIT_OBJECT, AUDIT_CELL, AUDIT_SLOTMAP, AUDIT_MATERIAL, AUDIT_SPACE, AUDIT_CREATURES,
+ AUDIT_CHUNKS, AUDIT_CHUNK_MISSING) = (1 << b for b in range(AUDIT_BITS))
+AUDIT_NAMES = ('NOT_RESET', 'REC', 'PLAYER', 'OBJECT', 'CELL', 'SLOTMAP', 'MATERIAL', 'SPACE', 'CREATURES', 'CHUNKS', 'CHUNK_MISSING')
+
+NAV_MAX_TARGETS = 16  # target sets per navigation query (crafter_hip_navigate.h CRAFTER_NAV_MAX_TARGETS)
 
 # texture slots of TablePtrs.tex_tile (crafter_hip_types.h CRAFTER_TEX_*)
 TEX_MATERIAL0 = 0

@@ -930,6 +930,49 @@ class BatchedEnv:
     self._fingerprint(0, mask, None, out)
     return out
 
+  # ------------------------------------------------------------------ the audit of the rows (include/crafter_hip_audit.h)
+  def audit(self, mask=None, out=None):
+    """(flags int32 [N], detail int32 [N, 4]) on the device: every table the step kernels derive from mat / objs / rec and then
+    trust -- the cell -> slot map where it is state, the five census columns per chunk, chunk_order / chunk_seen / nchunks_seen --
+    recounted from those three, one launch for the batch.  flags[e] = 0: row e is a row; else bit b names abi.AUDIT_NAMES[b]
+    (NOT_RESET, REC, PLAYER, OBJECT, CELL, SLOTMAP, MATERIAL, SPACE, CREATURES, CHUNKS, CHUNK_MISSING; crafter_hip_audit.h says
+    when each holds) and detail[e] = (bit, index, found, expected) of the lowest failing bit at its lowest offending slot, cell
+    x * H + y, census word chunk * 5 + column or chunk_order position (-1 where a value means nothing; four -1 for a consistent
+    row).  For rows written from outside -- edit tapes, load_state, WorldBank, copy_envs, pokes into `state` -- and for soaks:
+    check_errors() only reports what a kernel happened to notice.  Safe on garbage: nothing read from a row is used as an index
+    before it is bounded.  Read-only: it writes its outputs only, draws nothing from the RNG, sets no status bit, does not look
+    at the world pool.  Does not synchronise.  mask: rows with a zero byte are left untouched.  out = (flags, detail): contiguous
+    int32 device tensors of exactly those shapes to write into.  crafter_amd.audit_host is the numpy mirror."""
+    fn = _libmod.require(self._lib, 'crafter_audit', 'audit()')
+    shapes = (self.num_envs,), (self.num_envs, 4)
+    if out is None:
+      out = torch.zeros(shapes[0], dtype=torch.int32, device=self.device), torch.full(shapes[1], -1, dtype=torch.int32, device=self.device)
+    else:
+      if len(out) != 2:
+        raise ValueError('out must be a pair (flags, detail)')
+      for k, (t, shape) in enumerate(zip(out, shapes)):
+        self._out(t, shape, torch.int32, f'out[{k}]')
+    mask, mptr = self._mask(mask, check_len=True)
+    flags, detail = out
+    self._call(fn, mptr, _ptr(flags), _ptr(detail))
+    self._keep = mask
+    return flags, detail
+
+  def assert_consistent(self, mask=None, limit=4):
+    """audit(mask), read back (synchronises): raises CrafterDeviceError naming the first `limit` inconsistent rows, the
+    invariants each fails and the detail of its lowest one."""
+    flags, detail = self.audit(mask)   # (rows the mask leaves out keep the fresh tensors' 0)
+    bad = torch.nonzero(flags).flatten()
+    if not bad.numel():
+      return
+    rows = []
+    for i in bad[:limit].tolist():
+      bits, (bit, index, found, expected) = int(flags[i]), detail[i].tolist()
+      names = [name for b, name in enumerate(abi.AUDIT_NAMES) if bits >> b & 1]
+      where = f' at chunk {index // 5} column {index % 5}' if bit in (7, 8) else ''
+      rows.append(f'env {i}: {", ".join(names)} ({abi.AUDIT_NAMES[bit]}: index {index}{where}, found {found}, expected {expected})')
+    raise CrafterDeviceError(f'{bad.numel()} inconsistent rows -- ' + '; '.join(rows))
+
   # ------------------------------------------------------------------ navigation queries (include/crafter_hip_navigate.h)
   @staticmethod
   def _class_set(names, entry, what):

@@ -19,9 +19,11 @@
 #include <vector>
 
 #include "../../include/crafter_hip.h"
+#include "../../include/crafter_hip_audit.h"
 #include "../../include/crafter_hip_edit.h"
 #include "../../include/crafter_hip_fingerprint.h"
 #include "../../include/crafter_hip_navigate.h"
+#include "audit.hpp"
 #include "crafter_rollout.hpp"
 #include "crafter_rollout_subset.hpp"
 #include "crafter_subset.hpp"
@@ -958,6 +960,32 @@ int crafter_navigate(crafter_handle* h, const uint8_t* mask, const uint32_t* tar
       hipLaunchKernelGGL(crafter_navigate_lds_kernel<0>, grid, block, lds, s, h->cfg, h->tb, h->st, mask, q, dist, first, facing);
   }
   return launched(h, "crafter_navigate launch");
+}
+
+// The audit of the rows as they stand on `stream` (audit.hpp): every derived table recounted from mat, objs and rec.  Like
+// crafter_symbolic it reads live rows only and waits for no batch of the pool; it sets no status bit.  One wave per env for
+// worlds of at most 64 x 64 cells and 256 slots, a workgroup of 256 threads beyond; objmap is audited where it is state.
+int crafter_audit(crafter_handle* h, const uint8_t* mask, int32_t* flags, int32_t* detail, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  if (ready(h, "crafter_audit")) return 1;
+  if (!flags || !detail) return fail(h, "crafter_audit: flags or detail is null");
+  const size_t lds = audit_lds_words(h->cfg) * 4;
+  if (lds > (size_t)kAuditMaxLds) return fail(h, "crafter_audit: the area's tables exceed 64 KiB of LDS");
+  if (adopt_stream(h, s)) return 1;
+  const dim3 grid((unsigned)h->cfg.num_envs);
+  const bool map = !h->plan.maps_in_lds;
+  if (audit_in_wave(h->cfg)) {
+    if (map)
+      hipLaunchKernelGGL((crafter_audit_kernel<kAuditThreads, 1>), grid, dim3(kAuditThreads), lds, s, h->cfg, h->tb, h->st, mask, flags, detail);
+    else
+      hipLaunchKernelGGL((crafter_audit_kernel<kAuditThreads, 0>), grid, dim3(kAuditThreads), lds, s, h->cfg, h->tb, h->st, mask, flags, detail);
+  } else {
+    if (map)
+      hipLaunchKernelGGL((crafter_audit_kernel<kAuditWideThreads, 1>), grid, dim3(kAuditWideThreads), lds, s, h->cfg, h->tb, h->st, mask, flags, detail);
+    else
+      hipLaunchKernelGGL((crafter_audit_kernel<kAuditWideThreads, 0>), grid, dim3(kAuditWideThreads), lds, s, h->cfg, h->tb, h->st, mask, flags, detail);
+  }
+  return launched(h, "crafter_audit launch");
 }
 
 // Edits of the n envs idx names, in place (env_edit.hpp): the index check of crafter_step_n_envs, then one workgroup per named

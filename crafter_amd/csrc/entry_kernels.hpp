@@ -407,6 +407,17 @@ crafter_navigate_lds_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_
   navigate_lds_body<WaveGfx950<kNavWideThreads>, MAP>(w, (uint32_t*)smem, (int)blockIdx.x, cfg, tb, st, mask, q, dist, first, facing);
 }
 
+// crafter_audit (audit.hpp): one workgroup per env, its tables in audit_lds_words(cfg) words of LDS.  NT 64 (one wave: worlds of
+// at most 64 x 64 cells and 256 slots) or 256.  MAP as for crafter_symbolic_kernel.
+template <int NT, int MAP>
+__global__ void __launch_bounds__(NT)
+crafter_audit_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, int32_t* __restrict__ flags,
+                     int32_t* __restrict__ detail) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  WaveGfx950<NT> w;
+  audit_body<WaveGfx950<NT>, MAP>(w, (uint32_t*)smem, (int)blockIdx.x, cfg, tb, st, mask, flags, detail);
+}
+
 // crafter_edit_envs (env_edit.hpp): one workgroup per named env, behind the index check of crafter_step_n_envs (a refused list:
 // every workgroup leaves at once, no row changes).  Workgroup b replays row b of the tape on env idx[b].
 __global__ void __launch_bounds__(kEditThreads)

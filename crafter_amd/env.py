@@ -233,6 +233,11 @@ class Env(BaseClass):
     dist, first, facing = self._batch.navigate(targets, passable)
     return dist[0].cpu().numpy(), first[0].cpu().numpy(), facing[0].cpu().numpy().astype(bool)
 
+  def audit(self):
+    """BatchedEnv.audit() for this env: the names (abi.AUDIT_NAMES) of the invariants its row fails; [] for a consistent one."""
+    bits = int(self._batch.audit()[0][0].item())
+    return [name for b, name in enumerate(abi.AUDIT_NAMES) if bits >> b & 1]
+
   def fingerprint(self, parts=abi.FP_DYNAMICS):
     """BatchedEnv.fingerprint(parts) for this env: the key as an unsigned Python int."""
     return int(self._batch.fingerprint(parts)[0].item()) & 0xFFFFFFFFFFFFFFFF

@@ -83,6 +83,7 @@ EXTENSIONS = {
     'crafter_fingerprint': ('crafter_hip_fingerprint.h', i32, [vp, vp, C.c_uint32, vp, vp, vp]),
     'crafter_navigate': ('crafter_hip_navigate.h', i32, [vp, vp, vp, i32, C.c_uint32, vp, vp, vp, vp]),
     'crafter_edit_envs': ('crafter_hip_edit.h', i32, [vp, vp, i32, vp, i32, vp]),
+    'crafter_audit': ('crafter_hip_audit.h', i32, [vp] * 5),
 }
 
 _lib = None

@@ -3,7 +3,8 @@ MI355X path: same flags, same prints (reset time, material counts, step time / F
 ``--envs N`` (not in the reference) runs N environments at once through BatchedEnv; ``--legal`` (not in the reference either)
 samples uniformly among the actions the legal-action mask allows instead of among all of them; ``--levels K`` (not in the
 reference) draws every episode from a level table of seeds 0 .. K-1 (BatchedEnv.set_levels); ``--worlds FILE.npz`` (not in the
-reference) plays the authored worlds of a bank saved by ``WorldBank.save`` instead of generated ones."""
+reference) plays the authored worlds of a bank saved by ``WorldBank.save`` instead of generated ones; ``--audit K`` (not in the
+reference) audits every row after every K-th step (BatchedEnv.assert_consistent) and stops with the finding."""
 import argparse
 import copy
 import time
@@ -30,6 +31,7 @@ def main(argv=None):
   parser.add_argument('--legal', action='store_true', help='sample uniformly among the legal actions (BatchedEnv.legal_actions)')
   parser.add_argument('--levels', type=int, default=0, help='draw every episode from a level table of seeds 0 .. K-1 (set_levels)')
   parser.add_argument('--worlds', type=str, default=None, help='play the authored worlds of a bank saved by WorldBank.save (reset(worlds=...))')
+  parser.add_argument('--audit', type=int, default=0, help='audit every row after every K-th step and stop with the finding (assert_consistent)')
   args = parser.parse_args(argv)
 
   import torch
@@ -39,6 +41,10 @@ def main(argv=None):
   rules['items']['health']['max'] = args.health       # run_random.py:21-22
   rules['items']['health']['initial'] = args.health
   random = np.random.RandomState(args.seed)
+
+  def audit(batch, step):   # --audit K: raises CrafterDeviceError naming the rows, the invariants they fail and where
+    if args.audit > 0 and step % args.audit == 0:
+      batch.assert_consistent()
 
   def legal_generator(device):   # --legal: torch.multinomial's stream, on the device the mask lives on
     generator = torch.Generator(device=device)
@@ -68,6 +74,7 @@ def main(argv=None):
       _, _, done, _ = env.step(actions, info=False)
       env.reset(mask=done, worlds=bank, world_ids=pick())   # no host round trip: the mask stays on the device
       steps += args.envs
+      audit(env, steps // args.envs)
       if steps // args.envs % 64 == 0:
         finished = int(env.records()['episode'].sum()) - args.envs
     torch.cuda.synchronize()
@@ -79,6 +86,7 @@ def main(argv=None):
 
   if args.envs == 1:
     env = Env(area=tuple(args.area), length=args.length, seed=args.seed, rules=rules)
+    batch = env._batch
     if args.record:   # run_random.py:24: crafter.Recorder(env, args.record) -> stats.jsonl
       env = EnvStatsRecorder(env, args.record)
     if args.levels:
@@ -100,6 +108,7 @@ def main(argv=None):
         else:
           action = random.randint(0, env.action_space.n)
         _, _, done, _ = env.step(action)
+        audit(batch, env._step)
       duration = time.time() - start
       step = env._step
       print(f'Step time: {1000 * duration / step:.2f}ms ({int(step / duration)} FPS)')
@@ -107,7 +116,7 @@ def main(argv=None):
     return
 
   seed = 0 if args.seed is None else args.seed
-  env = BatchedEnv(args.envs, area=tuple(args.area), length=args.length, seed=seed, rules=rules, auto_reset=True)
+  env = batch = BatchedEnv(args.envs, area=tuple(args.area), length=args.length, seed=seed, rules=rules, auto_reset=True)
   if args.levels:
     env.set_levels(list(range(args.levels)))
   if args.record:
@@ -127,6 +136,7 @@ def main(argv=None):
     _, _, done, _ = env.step(actions, info=False)
     finished += int(done.sum())
     steps += args.envs
+    audit(batch, steps // args.envs)
   torch.cuda.synchronize()
   duration = time.time() - start
   env.check_errors()

@@ -216,6 +216,118 @@ def navigate_host(snapshot, n_materials, targets, passable, move_actions):
   return dist, first, facing
 
 
+def _host_array(a, dtype):
+  """A raw buffer -- numpy array or torch tensor, on any device -- as a contiguous numpy array viewed as `dtype`."""
+  if hasattr(a, 'detach'):
+    a = a.detach().cpu().numpy()
+  a = np.ascontiguousarray(a)
+  return a if a.dtype == dtype else a.view(dtype)
+
+
+def audit_host(buffers, cfg, rules, slot_map_derived=True, mask=None):
+  """The numpy mirror of the device's audit (include/crafter_hip_audit.h) over raw buffers -- a downloaded BatchedEnv.state or a
+  CPU harness's buffers: mat, objs, rec, chunk_order, chunk_seen, census, and objmap unless slot_map_derived -> (flags int32 [N],
+  detail int32 [N, 4]), rows with a zero mask byte left at 0 / -1.  cfg: the batch's abi.Config; rules: its compiled rules
+  (n_materials, mat_grass, mat_path).  Written unlike the kernel on purpose -- per env, whole-array numpy, no shared counters --
+  and exact: the device computes the same integers, `detail` included."""
+  n, Wd, H, C = int(cfg.num_envs), int(cfg.W), int(cfg.H), int(cfg.max_objects)
+  cells, ncy = Wd * H, int(cfg.nchunk_y)
+  nch = int(cfg.nchunk_x) * ncy
+  mat_all = _host_array(buffers['mat'], np.uint8).reshape(n, cells)
+  objs_all = objs_view(_host_array(buffers['objs'], np.uint8).reshape(n, C, abi.OBJ_DTYPE.itemsize))
+  rec_all = rec_view(_host_array(buffers['rec'], np.uint8).reshape(n, abi.REC_DTYPE.itemsize))
+  order_all = _host_array(buffers['chunk_order'], np.uint16).reshape(n, nch)
+  seen_all = _host_array(buffers['chunk_seen'], np.uint8).reshape(n, nch)
+  census_all = _host_array(buffers['census'], np.int32).reshape(n, nch * 5)
+  objmap_all = None if slot_map_derived else _host_array(buffers['objmap'], np.uint16).reshape(n, cells)
+  cell_chunk = (np.arange(Wd)[:, None] // abi.CHUNK * ncy + np.arange(H)[None, :] // abi.CHUNK).reshape(-1)
+  flags, detail = np.zeros(n, np.int32), np.full((n, 4), -1, np.int32)
+  clamp = lambda v, lo, hi: min(max(int(v), lo), hi)
+  for e in range(n):
+    if mask is not None and not mask[e]:
+      continue
+    r = rec_all[e]
+    if r['episode'] == 0:
+      flags[e], detail[e] = abi.AUDIT_NOT_RESET, (0, -1, -1, -1)
+      continue
+    found = {}   # bit -> (index, found, expected) at the check's lowest offending index
+    ranges = ((r['nobj'], 1, C), (r['mt_pos'], 0, abi.MT_N), (r['step'], 0, int(cfg.n_daylight) - 1), (r['nchunks_seen'], 0, nch))
+    for field, (v, lo, hi) in enumerate(ranges):
+      if not lo <= v <= hi:
+        found[1] = (field, int(v), clamp(v, lo, hi))
+        break
+    nobj, k = clamp(r['nobj'], 1, C), clamp(r['nchunks_seen'], 0, nch)
+    mat, objs, order = mat_all[e], objs_all[e], order_all[e][:k].astype(np.int64)
+    # the chunk list
+    pos = np.full(nch, -1, np.int64)
+    for i in range(k - 1, -1, -1):
+      if order[i] < nch:
+        pos[order[i]] = i
+    bad_pos = [i for i in range(k) if order[i] >= nch or pos[order[i]] != i]
+    flagged = seen_all[e] != 0
+    bad_pos += [int(pos[c]) for c in np.nonzero((pos >= 0) & ~flagged)[0]]
+    unlisted = np.nonzero((pos < 0) & flagged)[0]
+    if bad_pos:
+      i = min(bad_pos)
+      listed_once = order[i] < nch and pos[order[i]] == i
+      found[9] = (i, 0, 1) if listed_once else (i, int(order[i]), -1)
+    elif len(unlisted):
+      found[9] = (-1, int(unlisted[0]), -1)
+    # the slot table
+    slots = np.arange(1, nobj)
+    live = slots[objs['type'][1:nobj] != abi.T_NONE]
+    lo = objs[live]
+    players = (lo['type'] == abi.T_PLAYER) != (live == 1)
+    bad_player = ([1] if nobj < 2 or objs['type'][1] == abi.T_NONE else []) + live[players].tolist()
+    if bad_player:
+      s = min(bad_player)
+      tp = int(objs['type'][s]) if s < nobj else 0
+      found[2] = (s, tp, abi.T_PLAYER if s == 1 else -1)
+    ok = (lo['type'] <= abi.T_PLANT) & (lo['x'] < Wd) & (lo['y'] < H)
+    if not ok.all():
+      s = int(live[~ok][0])
+      o = objs[s]
+      found[3] = ((s, int(o['type']), abi.T_PLANT) if o['type'] > abi.T_PLANT else (s, int(o['x']), Wd - 1) if o['x'] >= Wd else
+                  (s, int(o['y']), H - 1))
+    valid, vo = live[ok], lo[ok]
+    vcell = vo['x'].astype(np.int64) * H + vo['y']
+    per_cell = np.bincount(vcell, minlength=cells)
+    shared = np.nonzero(per_cell > 1)[0]
+    if len(shared):
+      found[4] = (int(shared[0]), int(per_cell[shared[0]]), 1)
+    if objmap_all is not None:
+      objmap = objmap_all[e]
+      wrong = objmap[vcell] != valid
+      if wrong.any():
+        c = int(vcell[wrong].min())
+        found[5] = (c, int(objmap[c]), int(valid[wrong & (vcell == c)].min()))
+      elif int((objmap != 0).sum()) != len(live):
+        found[5] = (-1, int((objmap != 0).sum()), len(live))
+    bad_mat = np.nonzero((mat < 1) | (mat > rules.n_materials))[0]
+    if len(bad_mat):
+      found[6] = (int(bad_mat[0]), int(mat[bad_mat[0]]), -1)
+    # the census
+    count = np.zeros((nch, 5), np.int64)
+    in_range = (mat >= 1) & (mat <= rules.n_materials)
+    count[:, 0] = np.bincount(cell_chunk[in_range & (mat == rules.mat_grass)], minlength=nch)
+    count[:, 1] = np.bincount(cell_chunk[in_range & (mat == rules.mat_path)], minlength=nch)
+    vchunk = cell_chunk[vcell]
+    for col, tp in ((2, abi.T_ZOMBIE), (3, abi.T_SKELETON), (4, abi.T_COW)):
+      count[:, col] = np.bincount(vchunk[vo['type'] == tp], minlength=nch)
+    stale = np.nonzero(census_all[e] != count.reshape(-1))[0]
+    for bit, cols in ((7, stale[stale % 5 < 2]), (8, stale[stale % 5 >= 2])):
+      if len(cols):
+        found[bit] = (int(cols[0]), int(census_all[e][cols[0]]), int(count.reshape(-1)[cols[0]]))
+    missing = valid[pos[vchunk] < 0]
+    if len(missing):
+      s = int(missing[0])
+      found[10] = (s, int(cell_chunk[int(objs['x'][s]) * H + int(objs['y'][s])]), -1)
+    if found:
+      low = min(found)
+      flags[e], detail[e] = sum(1 << b for b in found), (low,) + found[low]
+  return flags, detail
+
+
 def levels_cum(weights):
   """K weights (non-negative, not all zero) -> cum uint32 [K], cum[j] = min(floor(2^32 * sum(w[:j + 1]) / sum(w)), 2^32 - 1),
   in exact rational arithmetic."""
