@@ -9,7 +9,8 @@ from .lib import CrafterLibError  # noqa: F401
 from .abi import (FP_ALL, FP_CHUNKS, FP_CLOCK, FP_DYNAMICS, FP_IDENT, FP_MAP, FP_OBJECTS, FP_PARTS, FP_PLAYER, FP_RNG,  # noqa: F401
                   FP_VISIBLE, NAV_MAX_TARGETS)
 from .abi import AUDIT_NAMES  # noqa: F401
-from .state import audit_host, fingerprint_host, levels_pick, navigate_host  # noqa: F401
+from .abi import NEARBY_CLIP, NEARBY_COLUMNS, NEARBY_MAX_ENTS, NEARBY_NUMPY  # noqa: F401
+from .state import audit_host, fingerprint_host, levels_pick, navigate_host, nearby_host  # noqa: F401
 from .worlds import WorldBank  # noqa: F401
 from . import edits  # noqa: F401
 from .recorder import BatchedEpisodeRecorder, BatchedStatsRecorder, EnvStatsRecorder  # noqa: F401

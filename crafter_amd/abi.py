@@ -68,6 +68,13 @@ AUDIT_NAMES = ('NOT_RESET', 'REC', 'PLAYER', 'OBJECT', 'CELL', 'SLOTMAP', 'MATER
 
 NAV_MAX_TARGETS = 16  # target sets per navigation query (crafter_hip_navigate.h CRAFTER_NAV_MAX_TARGETS)
 
+# nearby queries (crafter_hip_nearby.h CRAFTER_NEARBY_*): the two window rules, the entity list's rows and its columns
+NEARBY_CLIP, NEARBY_NUMPY = 0, 1
+NEARBY_MAX_ENTS = 32
+NEARBY_ROW = 6
+NEARBY_MAX_SIDE = 512
+NEARBY_COLUMNS = ('class', 'dx', 'dy', 'health', 'facing', 'aux')
+
 # texture slots of TablePtrs.tex_tile (crafter_hip_types.h CRAFTER_TEX_*)
 TEX_MATERIAL0 = 0
 (TEX_PLAYER_LEFT, TEX_PLAYER_RIGHT, TEX_PLAYER_UP, TEX_PLAYER_DOWN, TEX_PLAYER_SLEEP, TEX_COW,

@@ -1050,6 +1050,81 @@ class BatchedEnv:
     self._keep = mask
     return dist, first, facing
 
+  # ------------------------------------------------------------------ nearby queries (include/crafter_hip_nearby.h)
+  @staticmethod
+  def _check_nearby(class_names, n_materials, area, max_objects, distance=None, k=16, classes=None, numpy_slices=False):
+    """The host side of nearby(), callable without a device: -> (distance, flags, the class set) as ints.  class_names:
+    symbolic_names['classes'].  ValueError before anything is enqueued: k outside 0 .. NEARBY_MAX_ENTS, a distance that is no
+    integer, numpy_slices with the whole world, an unknown name, a class that is no object class, more than 31 classes, and
+    with k > 0 a world with a side above NEARBY_MAX_SIDE or more slots than the kernel's key table holds."""
+    names = list(class_names)
+    if len(names) > 31:
+      raise ValueError(f'nearby() holds a class set in 32 bits: {len(names)} classes are too many')
+    integer = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not integer(k) or not 0 <= k <= abi.NEARBY_MAX_ENTS:
+      raise ValueError(f'k must be an integer in 0 .. {abi.NEARBY_MAX_ENTS}, not {k!r}')
+    if distance is not None and not integer(distance):
+      raise ValueError(f'distance must be None (the whole world) or an integer, not {distance!r}')
+    d = -1 if distance is None or distance < 0 else int(min(distance, 1 << 20))
+    if numpy_slices and d < 0:
+      raise ValueError('numpy_slices needs a distance >= 0: the reference has no slice for the whole world')
+    objects = 0x3F << (n_materials + 1)
+    if classes is None:
+      bits = objects & ~(1 << (n_materials + abi.T_PLAYER))
+    elif isinstance(classes, (list, tuple, set, frozenset)) and not len(classes):
+      bits = 0
+    else:
+      bits = BatchedEnv._class_set(names, classes, 'classes')
+    if bits & ~objects:
+      raise ValueError(f'classes: only the object classes {names[n_materials + 1:]} can be listed')
+    if k > 0 and (max(area) > abi.NEARBY_MAX_SIDE or (40 + 32 + max_objects) * 4 > 64 * 1024):
+      raise ValueError(f'nearby(k > 0) serves worlds of at most {abi.NEARBY_MAX_SIDE} cells a side and about 16000 slots; k=0 gives the counts')
+    return d, abi.NEARBY_NUMPY if numpy_slices else abi.NEARBY_CLIP, bits
+
+  def nearby(self, distance=None, k=16, classes=None, numpy_slices=False, mask=None, out=None):
+    """(counts int32 [N, C], ents int16 [N, k, 6], n int32 [N]) on the device: what World.nearby(player.pos, distance) and
+    World.count say about every env (engine.py:95-110), and the k nearest objects.  The window is the square of cells within
+    `distance` of the player on both axes, clipped to the world; None (or a negative distance): the whole world.
+    numpy_slices=True: exactly the cells the reference's own `_mat_map[x - d: x + d + 1, y - d: y + d + 1]` selects -- EMPTY one
+    or two cells from the west or north border, which is why the reference cannot craft there.  counts, in the class ids of
+    symbolic_names['classes'] (C = len of it): [e, 0] the cells of the window, [e, m] the window cells of material m whatever
+    stands on them, [e, n_materials + t] the live objects of type t in the window, the player included.  ents[e, j], j < min(n[e],
+    k): the j-th nearest object whose class is in `classes` -- names, ids or a list of them as navigate() takes; default every
+    object class but the player; [] none -- in ascending dx^2 + dy^2, then dx, then dy, as abi.NEARBY_COLUMNS = (class id, dx, dy,
+    health, facing code, aux): the facing code is symbolic()'s plane-1 variant (arrow 1 .. 4, ripe plant 1, else 0), aux is
+    saturated to int16.  n[e] counts every object that qualified and may exceed k; rows from min(n, k) on are zeros.  k = 0 skips
+    the list (ents has no rows, n is zeros).  A row never reset gives zeros.  After a step() that auto-reset an env the row
+    describes the new episode's first state, after a rollout() the state behind its last step.  Read-only: no draw from the
+    envs' RNG, no byte of state changes, no wait for the world pool.  Does not synchronise.  mask: rows with a zero byte are left
+    untouched.  out = (counts, ents, n): contiguous device tensors of exactly those dtypes and shapes to write into.  Bad
+    arguments raise ValueError before anything is enqueued.  crafter_amd.nearby_host is the numpy mirror."""
+    fn = _libmod.require(self._lib, 'crafter_nearby', 'nearby()')
+    names = self.symbolic_names['classes']
+    d, flags, bits = self._check_nearby(names, len(self.rules['materials']), (self.cfg.W, self.cfg.H), self.cfg.max_objects,
+                                        distance, k, classes, numpy_slices)
+    shapes = ((self.num_envs, len(names)), torch.int32), ((self.num_envs, k, abi.NEARBY_ROW), torch.int16), ((self.num_envs,), torch.int32)
+    if out is None:
+      out = tuple(torch.zeros(shape, dtype=dt, device=self.device) for shape, dt in shapes)
+    else:
+      if len(out) != 3:
+        raise ValueError('out must be a triple (counts, ents, n)')
+      for j, (t, (shape, dt)) in enumerate(zip(out, shapes)):
+        self._out(t, shape, dt, f'out[{j}]')
+    mask, mptr = self._mask(mask, check_len=True)
+    counts, ents, n = out
+    self._call(fn, mptr, d, flags, bits, k, _ptr(counts), _ptr(ents) if k else None, _ptr(n) if k else None)
+    self._keep = mask
+    return counts, ents, n
+
+  def count(self, material):
+    """World.count(material) of every env (engine.py:109-110): int32 [N] on the device, a view of one whole-world nearby(k=0)
+    call.  material: a name of rules['materials'] or its id."""
+    names = ['none'] + list(self.rules['materials'])
+    bits = self._class_set(names, material, 'material')
+    if bits & (bits - 1):
+      raise ValueError('material: one name or id')
+    return self.nearby(None, k=0)[0][:, bits.bit_length() - 1]
+
   def info(self):
     """Device-tensor views of what the reference puts into ``info`` (env.py:108-115)."""
     o, r = self._off, self._rec_i32

@@ -23,7 +23,7 @@ UNITS = [(SRC.name, []), (SRC_ROLLOUT.name, ROLLOUT_FLAGS), (SRC_SUBSET.name, []
 def sources():
   return ([ROOT / 'csrc' / name for name, _ in UNITS] + sorted((ROOT / 'csrc').glob('*.hpp')) + sorted((ROOT / 'csrc').glob('*.inc')) +
           [ROOT.parent / 'include' / name for name in ('crafter_hip.h', 'crafter_hip_types.h', 'crafter_hip_fingerprint.h', 'crafter_hip_navigate.h', 'crafter_hip_edit.h',
-                                                    'crafter_hip_audit.h')])
+                                                    'crafter_hip_audit.h', 'crafter_hip_nearby.h')])
 
 
 def source_hash():

@@ -23,6 +23,7 @@
 #include "../../include/crafter_hip_edit.h"
 #include "../../include/crafter_hip_fingerprint.h"
 #include "../../include/crafter_hip_navigate.h"
+#include "../../include/crafter_hip_nearby.h"
 #include "audit.hpp"
 #include "crafter_rollout.hpp"
 #include "crafter_rollout_subset.hpp"
@@ -37,6 +38,7 @@
 #include "launch_plan.hpp"
 #include "legal.hpp"
 #include "navigate.hpp"
+#include "nearby.hpp"
 #include "symbolic.hpp"
 #include "wave_gfx950.hpp"
 
@@ -986,6 +988,34 @@ int crafter_audit(crafter_handle* h, const uint8_t* mask, int32_t* flags, int32_
       hipLaunchKernelGGL((crafter_audit_kernel<kAuditWideThreads, 0>), grid, dim3(kAuditWideThreads), lds, s, h->cfg, h->tb, h->st, mask, flags, detail);
   }
   return launched(h, "crafter_audit launch");
+}
+
+// The nearby query of the envs as they stand on `stream` (nearby.hpp): class counts over a window around the player and the k
+// nearest objects.  Like crafter_symbolic it reads live rows only and waits for no batch of the pool.  One wave per env for worlds
+// of at most 64 x 64 cells, a workgroup of 256 threads beyond; the object pass may walk objmap where it is state.
+int crafter_nearby(crafter_handle* h, const uint8_t* mask, int32_t distance, int32_t flags, uint32_t classes, int32_t k,
+                   int32_t* counts, int16_t* ents, int32_t* n, void* stream) {
+  const hipStream_t s = (hipStream_t)stream;
+  if (ready(h, "crafter_nearby")) return 1;
+  if (const int why = near_check(h->cfg, h->n_materials, distance, flags, classes, k, counts, ents, n))
+    return fail(h, std::string("crafter_nearby: ") + near_error_text(why));
+  const NearQuery q = {distance, flags, classes, k, -1};
+  const size_t lds = near_lds_words(h->cfg, k) * 4;
+  if (adopt_stream(h, s)) return 1;
+  const dim3 grid((unsigned)h->cfg.num_envs);
+  const bool map = !h->plan.maps_in_lds;
+  if (near_in_wave(h->cfg)) {
+    if (map)
+      hipLaunchKernelGGL((crafter_nearby_kernel<kNearThreads, 1>), grid, dim3(kNearThreads), lds, s, h->cfg, h->tb, h->st, mask, q, counts, ents, n);
+    else
+      hipLaunchKernelGGL((crafter_nearby_kernel<kNearThreads, 0>), grid, dim3(kNearThreads), lds, s, h->cfg, h->tb, h->st, mask, q, counts, ents, n);
+  } else {
+    if (map)
+      hipLaunchKernelGGL((crafter_nearby_kernel<kNearWideThreads, 1>), grid, dim3(kNearWideThreads), lds, s, h->cfg, h->tb, h->st, mask, q, counts, ents, n);
+    else
+      hipLaunchKernelGGL((crafter_nearby_kernel<kNearWideThreads, 0>), grid, dim3(kNearWideThreads), lds, s, h->cfg, h->tb, h->st, mask, q, counts, ents, n);
+  }
+  return launched(h, "crafter_nearby launch");
 }
 
 // Edits of the n envs idx names, in place (env_edit.hpp): the index check of crafter_step_n_envs, then one workgroup per named

@@ -418,6 +418,17 @@ crafter_audit_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __re
   audit_body<WaveGfx950<NT>, MAP>(w, (uint32_t*)smem, (int)blockIdx.x, cfg, tb, st, mask, flags, detail);
 }
 
+// crafter_nearby (nearby.hpp): one workgroup per env, its counters and sort keys in near_lds_words(cfg, q.k) words of LDS.  NT 64
+// (one wave: worlds of at most 64 x 64 cells) or 256.  MAP as for crafter_symbolic_kernel.  The query travels by value.
+template <int NT, int MAP>
+__global__ void __launch_bounds__(NT)
+crafter_nearby_kernel(Config cfg, TablePtrs tb, StatePtrs st, const uint8_t* __restrict__ mask, NearQuery q, int32_t* __restrict__ counts,
+                      int16_t* __restrict__ ents, int32_t* __restrict__ n) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  WaveGfx950<NT> w;
+  nearby_body<WaveGfx950<NT>, MAP>(w, (uint32_t*)smem, (int)blockIdx.x, cfg, tb, st, mask, q, counts, ents, n);
+}
+
 // crafter_edit_envs (env_edit.hpp): one workgroup per named env, behind the index check of crafter_step_n_envs (a refused list:
 // every workgroup leaves at once, no row changes).  Workgroup b replays row b of the tape on env idx[b].
 __global__ void __launch_bounds__(kEditThreads)

@@ -128,7 +128,7 @@ struct crafter_handle {
                                        // every kernel that seeds a world takes it as a launch argument (null: no table yet)
   int32_t* subset_actions = nullptr;   // crafter_step_envs: [N] the call's actions scattered to their envs' rows (step_body reads actions[env])
   int32_t* rollout_row_of = nullptr;   // crafter_step_n_envs: [N] the row of the call's compact outputs each named env writes (its place in idx)
-  int n_materials = 0;                 // crafter_navigate: the uploaded rules' material count (its class sets are checked on the host)
+  int n_materials = 0;                 // crafter_navigate, crafter_nearby: the uploaded rules' material count (their class sets are checked on the host)
   // optional per-kernel timing (HIP events on the launch stream)
   bool timing = false;
   std::vector<hipEvent_t> events;   // triples: before step, between, after reset

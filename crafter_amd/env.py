@@ -233,6 +233,13 @@ class Env(BaseClass):
     dist, first, facing = self._batch.navigate(targets, passable)
     return dist[0].cpu().numpy(), first[0].cpu().numpy(), facing[0].cpu().numpy().astype(bool)
 
+  def nearby(self, distance=None, k=16, classes=None, numpy_slices=False):
+    """BatchedEnv.nearby(...) for this env: (counts int32 [C], ents int16 [k, 6], n) as numpy arrays and an int, plus the counts
+    as a {class name: count} dict ('none': the cells of the window) -- World.nearby and World.count of the reference in one call."""
+    counts, ents, n = self._batch.nearby(distance, k, classes, numpy_slices)
+    counts = counts[0].cpu().numpy()
+    return counts, ents[0].cpu().numpy(), int(n[0].item()), dict(zip(self._batch.symbolic_names['classes'], counts.tolist()))
+
   def audit(self):
     """BatchedEnv.audit() for this env: the names (abi.AUDIT_NAMES) of the invariants its row fails; [] for a consistent one."""
     bits = int(self._batch.audit()[0][0].item())

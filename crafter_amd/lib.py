@@ -84,6 +84,7 @@ EXTENSIONS = {
     'crafter_navigate': ('crafter_hip_navigate.h', i32, [vp, vp, vp, i32, C.c_uint32, vp, vp, vp, vp]),
     'crafter_edit_envs': ('crafter_hip_edit.h', i32, [vp, vp, i32, vp, i32, vp]),
     'crafter_audit': ('crafter_hip_audit.h', i32, [vp] * 5),
+    'crafter_nearby': ('crafter_hip_nearby.h', i32, [vp, vp, i32, i32, C.c_uint32, i32, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@ MI355X path: same flags, same prints (reset time, material counts, step time / F
 samples uniformly among the actions the legal-action mask allows instead of among all of them; ``--levels K`` (not in the
 reference) draws every episode from a level table of seeds 0 .. K-1 (BatchedEnv.set_levels); ``--worlds FILE.npz`` (not in the
 reference) plays the authored worlds of a bank saved by ``WorldBank.save`` instead of generated ones; ``--audit K`` (not in the
-reference) audits every row after every K-th step (BatchedEnv.assert_consistent) and stops with the finding."""
+reference) audits every row after every K-th step (BatchedEnv.assert_consistent) and stops with the finding; ``--census`` (not in
+the reference) prints the reference's three "exist" lines for every env after the reset, from one BatchedEnv.nearby call."""
 import argparse
 import copy
 import time
@@ -32,6 +33,7 @@ def main(argv=None):
   parser.add_argument('--levels', type=int, default=0, help='draw every episode from a level table of seeds 0 .. K-1 (set_levels)')
   parser.add_argument('--worlds', type=str, default=None, help='play the authored worlds of a bank saved by WorldBank.save (reset(worlds=...))')
   parser.add_argument('--audit', type=int, default=0, help='audit every row after every K-th step and stop with the finding (assert_consistent)')
+  parser.add_argument('--census', action='store_true', help='print the three "exist" lines for every env after the reset, from one nearby() call')
   args = parser.parse_args(argv)
 
   import torch
@@ -45,6 +47,17 @@ def main(argv=None):
   def audit(batch, step):   # --audit K: raises CrafterDeviceError naming the rows, the invariants they fail and where
     if args.audit > 0 and step % args.audit == 0:
       batch.assert_consistent()
+
+  def census(batch):   # --census: World.count of coal, iron and diamond for every env, one launch and one download
+    if not args.census:
+      return
+    names = batch.symbolic_names['classes']
+    counts = batch.nearby(None, k=0)[0].cpu().numpy()
+    for e, row in enumerate(counts):
+      print(f'Env {e}:')
+      print('Coal exist:    ', int(row[names.index('coal')]))
+      print('Iron exist:    ', int(row[names.index('iron')]))
+      print('Diamonds exist:', int(row[names.index('diamond')]))
 
   def legal_generator(device):   # --legal: torch.multinomial's stream, on the device the mask lives on
     generator = torch.Generator(device=device)
@@ -64,6 +77,7 @@ def main(argv=None):
     env.reset(worlds=bank, world_ids=pick())
     torch.cuda.synchronize()
     print(f'Reset time: {1000 * (time.time() - start):.2f}ms for {args.envs} envs into {len(bank)} authored worlds')
+    census(env)
     finished, steps = 0, 0
     start = time.time()
     while finished < args.episodes * args.envs:
@@ -100,6 +114,7 @@ def main(argv=None):
       print('Coal exist:    ', env._world.count('coal'))
       print('Iron exist:    ', env._world.count('iron'))
       print('Diamonds exist:', env._world.count('diamond'))
+      census(batch)
       start = time.time()
       done = False
       while not done:
@@ -126,6 +141,7 @@ def main(argv=None):
   env.reset()
   torch.cuda.synchronize()
   print(f'Reset time: {1000 * (time.time() - start):.2f}ms for {args.envs} envs')
+  census(batch)
   finished, steps = 0, 0
   start = time.time()
   while finished < args.episodes * args.envs:

@@ -216,6 +216,55 @@ def navigate_host(snapshot, n_materials, targets, passable, move_actions):
   return dist, first, facing
 
 
+def nearby_host(snapshot, n_materials, distance=None, k=16, classes=None, numpy_slices=False):
+  """The numpy mirror of the device's nearby query (include/crafter_hip_nearby.h) over a snapshot() dict -- BatchedEnv.snapshot(i),
+  OracleEnv.snapshot() or a CPU harness's -> (counts int32 [1 + n_materials + 6], ents int16 [k, 6], n).  distance: None or
+  negative for the whole world; classes: a class set as an int (bit c = class c; None: every object class but the player);
+  numpy_slices: the window is what the reference's own expression selects (engine.py:97-98), evaluated here by numpy itself.
+  Written unlike the kernel on purpose: a boolean window, a bincount, a sort of tuples."""
+  mat = np.asarray(snapshot['mat'])
+  W, H = mat.shape
+  nm, k = int(n_materials), int(k)
+  if not 0 <= k <= abi.NEARBY_MAX_ENTS:
+    raise ValueError(f'k must lie in 0 .. {abi.NEARBY_MAX_ENTS}')
+  objects = 0x3F << (nm + 1)
+  classes = objects & ~(1 << (nm + abi.T_PLAYER)) if classes is None else int(classes)
+  if classes & ~objects:
+    raise ValueError('classes names a class that is no object class')
+  d = -1 if distance is None else int(distance)
+  if numpy_slices and d < 0:
+    raise ValueError('numpy_slices takes a distance >= 0')
+  counts, ents = np.zeros(nm + 1 + abi.T_PLANT, np.int32), np.zeros((k, abi.NEARBY_ROW), np.int16)
+  player = next((o for o in snapshot['objects'] if o[0] == abi.T_PLAYER), None)
+  if not snapshot.get('episode', 1) or player is None:
+    return counts, ents, 0
+  px, py = int(player[1]), int(player[2])
+  window = np.zeros((W, H), bool)
+  if numpy_slices:
+    window[px - d: px + d + 1, py - d: py + d + 1] = True
+  elif d < 0:
+    window[:] = True
+  else:
+    window[max(px - d, 0): px + d + 1, max(py - d, 0): py + d + 1] = True
+  counts[0] = window.sum()
+  counts[1: nm + 1] = np.bincount(mat[window].astype(np.int64), minlength=nm + 1)[1: nm + 1]
+  rows = []
+  for tp, x, y, health, fx, fy, aux in snapshot['objects']:
+    if not window[x, y]:
+      continue
+    counts[nm + tp] += 1
+    if classes >> (nm + tp) & 1:
+      face = 1 if fx < 0 else 2 if fx > 0 else 3 if fy < 0 else 4
+      code = ((5 if snapshot['sleeping'] else face) if tp == abi.T_PLAYER else face if tp == abi.T_ARROW else
+              int(aux > 300) if tp == abi.T_PLANT else 0)
+      dx, dy = x - px, y - py
+      rows.append((dx * dx + dy * dy, dx, dy, nm + tp, health, code, min(max(int(aux), -32768), 32767)))
+  rows.sort()
+  for j, (_, dx, dy, cls, health, code, aux) in enumerate(rows[:k]):
+    ents[j] = (cls, dx, dy, health, code, aux)
+  return counts, ents, len(rows)
+
+
 def _host_array(a, dtype):
   """A raw buffer -- numpy array or torch tensor, on any device -- as a contiguous numpy array viewed as `dtype`."""
   if hasattr(a, 'detach'):
